@@ -9,7 +9,9 @@ random-init weights, bf16 compute / fp32 master weights.  Data parallel over
 N GPUs = one process per GPU, RCCL all-reduce of gradient buckets overlapped
 with backward (weak scaling: the per-GPU batch is fixed).
 
-    python bench.py                       # 1 GPU, defaults
+    python bench.py                       # 1 GPU, defaults: set up, warm up, time the steps, one JSON line
+    python bench.py --full                # + the figures that take work of their own (see --full)
+    python bench.py --dump-outputs DIR    # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 5
 
@@ -74,6 +76,12 @@ def parse():
     ap.add_argument("--force-allreduce", action="store_true",
                     help="create the process group even at 1 rank and issue the bucketed all-reduces "
                          "(exercises the RCCL path from the gradient hooks on a 1-GPU box)")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the device's bf16 peak from rocminfo "
+                         "(pct_bf16_peak) and the bucketed all-reduce timed on its own (dist.allreduce_ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its loss, the "
+                         "gradients and the updated parameters) as DIR/<name>.npy in float32")
     return ap.parse_args()
 
 
@@ -114,6 +122,26 @@ def _peak_bf16_tflops(dev) -> float | None:
     except Exception:  # noqa: BLE001 - rocminfo missing: use the gfx950 spec clock
         pass
     return cus * 4 * 1024 * mhz * 1e6 / 1e12
+
+
+DUMP_MAX_BYTES = 64 << 20     # all of --dump-outputs together
+
+
+def _dump_outputs(path: str, arrays: dict) -> None:
+    """Write ``arrays`` (name -> tensor) as float32 ``<name>.npy`` files under ``path``.  When
+    they exceed DUMP_MAX_BYTES together, every array larger than its equal share is cut down to
+    a fixed, seeded sample of its elements (the same indices in every run)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // 4 // max(len(arrays), 1)
+    over = sum(t.numel() for t in arrays.values()) * 4 > DUMP_MAX_BYTES
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).reshape(-1).numpy()
+        if over and a.size > share:
+            idx = np.sort(np.random.default_rng(20240229).choice(a.size, size=share, replace=False))
+            a = a[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def main():
@@ -294,15 +322,27 @@ def main():
         per = [float(t.item()) for t in ts]
         elapsed = max(per)                     # the job's time is the slowest rank's
         rank_ms = [round(v / max(args.steps, 1) * 1e3, 3) for v in per]
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step receives: the loss it returns, and the gradients and the
+        # updated parameters it leaves behind (rank 0's; after the all-reduce every rank's are equal)
+        if args.impl == "native":
+            got = {"loss": loss, "grads": flat.grad, "params": flat.data}
+        else:
+            ps = [p for p in model.parameters() if p.requires_grad]
+            got = {"loss": loss, "params": torch.cat([p.detach().reshape(-1).float() for p in ps]),
+                   "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float()
+                                       for p in ps])}
+        if loss is not None:
+            _dump_outputs(args.dump_outputs, got)
     # communication diagnostics, measured AFTER the timed region: the bucketed
     # all-reduce of the whole gradient on its own (what the overlap has to hide)
     allreduce_ms = None
     n_buckets = None
     if bucketer is not None:
         n_buckets = bucketer.n_buckets
-        if bucketer.active:
+        if bucketer.active and args.full:
             allreduce_ms = bucketer.time_allreduce()
-    peak = _peak_bf16_tflops(dev)
+    peak = _peak_bf16_tflops(dev) if args.full else None
     ms = elapsed / max(args.steps, 1) * 1e3
     value = args.steps * B * world / elapsed
     base = TORCH_BASELINE_SAMPLES_PER_S_PER_GPU

@@ -25,7 +25,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   rc=$?; ok $rc || exit $rc
 fi
 step bench_native 300 python bench.py --steps "$STEPS" --warmup 5; rc=$?; ok $rc || exit $rc
-step bench_forced_rccl 300 python bench.py --steps "$STEPS" --warmup 5 --force-allreduce; rc=$?; ok $rc || exit $rc
+step bench_forced_rccl 300 python bench.py --steps "$STEPS" --warmup 5 --force-allreduce --full; rc=$?; ok $rc || exit $rc
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   step prof_rccl 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_rccl -o run -- \
     python3 bench.py --steps 5 --warmup 2 --force-allreduce --bucket-mb 4

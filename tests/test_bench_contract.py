@@ -45,6 +45,27 @@ def test_bench_single_process_json():
     _check(r, 1, 2, 1)
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's loss / gradients / parameters as float32 .npy,
+    identically from run to run; --full runs and keeps the plain keys."""
+    import numpy as np
+
+    base = [sys.executable, "bench.py", "--device", "cpu", "--tiny", "--steps", "2", "--warmup", "1", "--batch", "16"]
+    a, b = tmp_path / "a", tmp_path / "b"
+    r = _run(base + ["--dump-outputs", str(a)])
+    _check(_run(base + ["--full", "--dump-outputs", str(b)]), 1, 2, 1)
+    assert sorted(p.name for p in a.iterdir()) == ["grads.npy", "loss.npy", "params.npy"]
+    total = 0
+    for name in ("loss", "grads", "params"):
+        x, y = np.load(a / f"{name}.npy"), np.load(b / f"{name}.npy")
+        assert x.dtype == np.float32 and np.isfinite(x).all() and x.size > 0
+        assert np.array_equal(x, y), name
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.load(a / "loss.npy").item() == pytest.approx(r["final_loss"], abs=1e-4)
+    assert np.abs(np.load(a / "grads.npy")).max() > 0
+
+
 @pytest.mark.slow
 def test_bench_two_ranks_gloo_json():
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",

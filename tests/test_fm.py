@@ -14,7 +14,9 @@ import pytest
 from featurenet_amd.fm import extend, splot
 from featurenet_amd.fm.products import ProductSet
 
-REF = "/root/reference"
+from _golden import ref_dir
+
+REF = ref_dir()      # tests/golden/reference, unpacked
 need_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present")
 
 

@@ -9,7 +9,9 @@ from featurenet_amd.ir.compile import CompileError, ModelTooLarge, compile_model
 from featurenet_amd.ir.parse import parse_feature_model
 from featurenet_amd.ir.spec import ModelSpec
 
-REF = "/root/reference"
+from _golden import ref_dir
+
+REF = ref_dir()      # tests/golden/reference, unpacked
 need_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present")
 
 

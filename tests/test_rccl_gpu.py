@@ -139,7 +139,7 @@ def test_bench_force_allreduce_captures_rccl_step(tmp_path):
     hook-issued collectives inside, no eager fallback, every bucket issued."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-allreduce", "--steps", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-allreduce", "--full", "--steps", "5",
                         "--warmup", "3"], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

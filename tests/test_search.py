@@ -7,7 +7,9 @@ import pytest
 from featurenet_amd.ir.parse import parse_feature_model
 from featurenet_amd.search.trial import TrialConfig, TrialScheduler, run_trial
 
-REF = "/root/reference"
+from _golden import ref_dir
+
+REF = ref_dir()      # tests/golden/reference, unpacked
 need_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present")
 
 

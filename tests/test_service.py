@@ -3,7 +3,9 @@ import os
 
 import pytest
 
-REF = "/root/reference"
+from _golden import ref_dir
+
+REF = ref_dir()      # tests/golden/reference, unpacked
 
 
 def test_store_concurrent_field_updates(tmp_path):

@@ -95,7 +95,9 @@ def test_feature_attribution_on_reference_products(tmp_path):
     import pytest
     from pathlib import Path
 
-    pdt = Path("/root/reference/datasets/10Products.pdt")
+    from _golden import ref_dir
+
+    pdt = Path(ref_dir()) / "datasets" / "10Products.pdt"
     if not pdt.exists():
         pytest.skip("reference product file not available")
     rep = _synthetic_report(tmp_path / "report.txt", n=10)
