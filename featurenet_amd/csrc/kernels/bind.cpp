@@ -110,15 +110,12 @@ int fn_cu_occupy(int, int, int, void*, hipStream_t);
 int fn_softmax_rows(const float*, float*, long long, int, int, const float*, hipStream_t);
 int fn_unpack_bits(const void*, void*, long long, hipStream_t);
 int fn_conv_tile(const void*, const void*, const void*, const void*, const void*, const float*, void*, float*,
-                 const int*, int, int, int, int, int*, hipStream_t, const void*, const float*, float, void*,
-                 const float*, void*, void*, int);
+                 const int*, int, int, int, int, int*, hipStream_t, const void*, const float*, float, void*);
 int fn_conv_tile_workers(const int*, int, int);
 int fn_conv_tile_slab_rows(const int*, int, int);
 void fn_conv_tile_grid_cap(int);
-void fn_conv_tile_set_wlds(int);
 void fn_conv_tile_set_schedule(int);
 int fn_conv_tile_schedule();
-int fn_conv_tile_wring(const int*, int, int, int, int);
 int fn_conv_tile_f8(const void*, const void*, const void*, const void*, const void*, const float*, const float*, void*,
                     float, const int*, int, int, int, int, int*, hipStream_t, const void*, void*);
 int fn_conv_tile_f8_supported(int, int, int);
@@ -264,8 +261,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("conv_tile", [](uintptr_t src, uintptr_t wpk, uintptr_t rowtab, uintptr_t ktab, uintptr_t zp, uintptr_t bias,
                         uintptr_t out, uintptr_t stats, std::vector<int> geom, int ncol, int act, int MT, int NT,
                         uintptr_t sched, uintptr_t st, std::vector<long long> ext, uintptr_t bny, uintptr_t bnp,
-                        float oscale, uintptr_t osc, long long osc_n, uintptr_t pst, uintptr_t pz, uintptr_t pmask,
-                        int pact, std::vector<long long> pext) {
+                        float oscale, uintptr_t osc, long long osc_n) {
     need(geom, 31, "conv_tile");
     check_tile(geom, ext, ncol, MT, "conv_tile", NT);
     // osc: block scales of an e4m3 output, one dword per output position
@@ -276,25 +272,15 @@ PYBIND11_MODULE(_C, m) {
     } else if (bny) {   // the relu-mask bytes: ext[5] = their count (one per 8 output columns)
       fits(ext, 5, view_extent(geom, ncol) / 8, "conv_tile", "mask");
     }
-    // the BN prologue: pext = {pst, pz, pmask} element counts -- [scale C][shift C] of the source's
-    // channels, z of the source's shape, one mask byte per 8 source elements
-    if (pst) {
-      if (pext.size() < 3) throw std::runtime_error("conv_tile: the BN prologue needs pext = {pst, pz, pmask}");
-      const long long nsrc = prod({geom[0], geom[1], geom[2], geom[3], geom[4]});
-      fits(pext, 0, 2LL * geom[4], "conv_tile", "pst");
-      if (pz) fits(pext, 1, nsrc, "conv_tile", "pz");
-      if (pmask) fits(pext, 2, nsrc / 8, "conv_tile", "pmask");
-    }
     chk(fn_conv_tile(P<const void*>(src), P<const void*>(wpk), P<const void*>(rowtab), P<const void*>(ktab),
                      P<const void*>(zp), P<const float*>(bias), P<void*>(out), P<float*>(stats), geom.data(), ncol,
                      act, MT, NT, P<int*>(sched), S(st), P<const void*>(bny), P<const float*>(bnp), oscale,
-                     P<void*>(osc), P<const float*>(pst), P<void*>(pz), P<void*>(pmask), pact),
+                     P<void*>(osc)),
         "conv_tile");
   }, py::arg("src"), py::arg("wpk"), py::arg("rowtab"), py::arg("ktab"), py::arg("zp"), py::arg("bias"), py::arg("out"),
      py::arg("stats"), py::arg("geom"), py::arg("ncol"), py::arg("act"), py::arg("MT"), py::arg("NT"),
      py::arg("sched"), py::arg("st"), py::arg("ext") = std::vector<long long>(), py::arg("bny") = 0,
-     py::arg("bnp") = 0, py::arg("oscale") = 0.f, py::arg("osc") = 0, py::arg("osc_n") = 0, py::arg("pst") = 0,
-     py::arg("pz") = 0, py::arg("pmask") = 0, py::arg("pact") = 0, py::arg("pext") = std::vector<long long>());
+     py::arg("bnp") = 0, py::arg("oscale") = 0.f, py::arg("osc") = 0, py::arg("osc_n") = 0);
   m.def("conv_tile_f8", [](uintptr_t src, uintptr_t wpk, uintptr_t rowtab, uintptr_t ktab, uintptr_t zp,
                            uintptr_t scale, uintptr_t bias, uintptr_t out, float oscale, std::vector<int> geom, int ncol,
                            int relu, int MT, int NT, uintptr_t st, uintptr_t sched, std::vector<long long> ext,
@@ -359,15 +345,9 @@ PYBIND11_MODULE(_C, m) {
     return fn_conv_tile_workers(geom.data(), ncol, NT);
   });
   m.def("conv_tile_grid_cap", [](int cap) { fn_conv_tile_grid_cap(cap); });   // (tests: grid independence)
-  // the LDS weight ring: -1 = FN_TILE_WLDS (default on), 0 off, 1 on (tests / A/B in one process)
-  m.def("conv_tile_set_wlds", [](int mode) { fn_conv_tile_set_wlds(mode); });
   // the BN-statistics tile schedule: -1 = FN_TILE_SCHED (default static), 0 static, 1 chunked
   m.def("conv_tile_set_schedule", [](int mode) { fn_conv_tile_set_schedule(mode); });
   m.def("conv_tile_schedule", [] { return fn_conv_tile_schedule(); });
-  m.def("conv_tile_wring", [](std::vector<int> geom, int ncol, int MT, int NT, int mask) {
-    need(geom, 31, "conv_tile_wring");
-    return fn_conv_tile_wring(geom.data(), ncol, MT, NT, mask);
-  });
   m.def("conv_tile_slab_rows", [](std::vector<int> geom, int ncol, int NT) {
     // rows of the BN-statistics slab a conv_tile launch with statistics writes (one per tile chunk)
     need(geom, 31, "conv_tile_slab_rows");

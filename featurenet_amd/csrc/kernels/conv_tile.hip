@@ -72,17 +72,15 @@
 // NCW: compute waves (4: one per SIMD, MT fragments each; 8: two per SIMD at MT / 2 -- the same
 // 4 * 8 fragment rows, so the same row tables -- where a partner wave can issue while the other
 // waits: the one-wave-per-SIMD k-loop ran its MFMAs at 72 % of its cycles)
-// WL (bf16): the weight fragments through an LDS ring of `wring` k-step slots that the loader wave
-// LDS-DMAs (one copy per workgroup instead of one per compute wave through L1), with per-k-step
-// counters in LDS for the hand-off (see the loader); wring = 0 / WL false: every compute wave
-// streams the fragments global -> VGPRs itself (the PD-deep register ring).
-// PRO: the BN prologue instances (xform_job below; opt-in, measured slower) -- a template flag so the
-// default instances carry none of its code (it doubled their SGPR spills)
+// (An LDS weight ring -- the loader LDS-DMAing the weight fragments for all compute waves -- and a BN
+// prologue -- the loader normalising each landed halo in LDS -- measured 1.5-2.3x slower in round 6
+// and were removed: profiles/r6_bn_prologue.md.  Every compute wave streams the weight fragments
+// global -> VGPRs itself, the PD-deep register ring.)
 // CHK: the instances with the chunked BN-statistics schedule (data parallelism); the others run the
 // static one only (the chunk walk's state cost the one-GPU instances ~25 SGPR spills and 1-4 % of
 // their time)
 template <int MT, int NT, int CPP, int DBG = 0, bool F8 = false, bool Q8O = false, bool I8 = false, bool BS = false,
-          int NCW = CT_NCW, bool WL = false, bool PRO = false, bool CHK = true>
+          int NCW = CT_NCW, bool CHK = true>
 __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsigned char* __restrict__ src,
                                                                const uint4* __restrict__ wp,
                                                                const int2* __restrict__ rowtab,
@@ -95,10 +93,7 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
                                                                const float* __restrict__ scale, float oscale,
                                                                const unsigned char* __restrict__ gmask,
                                                                const unsigned* __restrict__ xsc,
-                                                               unsigned char* __restrict__ osc, int chunk,
-                                                               int wring, const float* __restrict__ pst,
-                                                               bf16* __restrict__ pz,
-                                                               unsigned char* __restrict__ pmask, int pact) {
+                                                               unsigned char* __restrict__ osc, int chunk) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dsm[];
   static_assert(!BS || F8 || Q8O, "block scales: fp8 operands or an e4m3 output");
   constexpr int NTHR = 64 * (NCW + 1);
@@ -169,18 +164,6 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
       }
     }
   }
-  // WL: the weight ring after everything else; counters in the job area: [8] k-steps published
-  // (landed in the ring) by the loader, [12 + w] k-steps whose fragments compute wave w has read
-  static_assert(!WL || !F8, "the LDS weight ring is the bf16 kernel's");
-  constexpr unsigned WSLOT = NT * 1024u;         // bytes of one ring slot (NT 1-KB bf16 fragments)
-  const int ring_off = 2 * g.BUF + mask_off + ct_mask_lds(NCW * MT * 16, Ncol, gmask != nullptr);
-  int* s_wrdy = s_job + 8;
-  int* s_wdone = s_job + 12;
-  int* s_wabort = s_job + 9;                     // set by a wave whose bounded wait ran out: no more waits
-  // (relaxed workgroup-scope atomics: plain ds_read / ds_write that the compiler may not merge,
-  // drop or hoist out of a polling loop, and -- unlike volatile -- with no wait behind them)
-  auto ld_cnt = [](int* p) -> int { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
-  auto st_cnt = [](int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
   if constexpr (F8) {
     if (tid < NT * 16) {
       const int c = blockIdx.y * NT * 16 + tid;
@@ -217,9 +200,6 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
   // and read the zero page outside.
   auto dma_job = [&](int tile, int slice, int bufoff) {
     ct_dma_job<CPP, ESZ>(g, src, zp, dsm, s_pos, tile, slice, bufoff, lane, tdn, thn, twn);
-  };
-  auto dma_job_rows = [&](int tile, int slice, int bufoff, int r_lo, int r_hi) {
-    ct_dma_job<CPP, ESZ>(g, src, zp, dsm, s_pos, tile, slice, bufoff, lane, tdn, thn, twn, r_lo, r_hi);
   };
   // BS: the scale dwords of the job's halo positions into scale plane `which` (64 positions per
   // DMA row; positions outside the input read the zero page: scale 2^-127 on zero data)
@@ -268,97 +248,8 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
     }
   };
 
-  // BN prologue (pst != null; bf16 forward only, host-checked): the source is the PREVIOUS layer's
-  // pre-BN output y, and the layer's input is z = relu(y * scale + shift) per input channel
-  // (pst = [scale C][shift C]).  Once a job's halo has landed the loader rewrites it in LDS as z --
-  // the same fma, activation and bf16 rounding as bn_apply_kernel, so the conv sees the same bits --
-  // leaving the zero page's padding positions alone (the conv pads z, not y), and for the positions
-  // the tile OWNS (per dimension the input rows [t*T - pad, (t+1)*T - pad) of output tile t, the
-  // last tile also everything past them: every input position has exactly one owner) the first
-  // column block also writes z (pz, for the weight gradient) and the relu-mask byte of each 8
-  // channels (pmask, bit j = z_j > 0: the statistics identity of the backward, ops/bnfuse.py).
-  // bn_apply's separate pass over y -- and its re-read of y here -- disappears.
-  auto xform_job = [&](int tile, int slice, int bufoff) {
-    if constexpr (!F8 && PRO) {
-      if (!pst) return;
-      int t = __builtin_amdgcn_readfirstlane(tile);
-      const int tw_ = t % twn; t /= twn;
-      const int th_ = t % thn; t /= thn;
-      const int td_ = t % tdn;
-      const int n = t / tdn;
-      const int dlo = td_ * g.TD - g.pd, hlo = th_ * g.TH - g.ph, wlo = tw_ * g.TW - g.pw;
-      const int HD = g.TD + g.KD - 1;
-      const bool interior = dlo >= 0 && hlo >= 0 && wlo >= 0 && dlo + HD <= g.ID && hlo + HH <= g.IH &&
-                            wlo + HW <= g.IW;
-      // owned halo rows per dimension: [0, T) (all of them for the last tile)
-      const int od = td_ == tdn - 1 ? 255 : g.TD, oh = th_ == thn - 1 ? 255 : g.TH, ow = tw_ == twn - 1 ? 255 : g.TW;
-      const bool writer = blockIdx.y == 0 && (pz || pmask);
-      const long long nbase = (long long)n * g.ID * g.IH * g.IW;
-      // (the loader shares SIMD 0 with compute wave 0, whose MFMA stream wins the issue arbitration
-      // at equal priority: the transform -- on the loader's critical path -- runs at a raised one)
-      __builtin_amdgcn_s_setprio(2);
-      unsigned char* buf = dsm + bufoff + lane * 16;
-      // the slice's scale / shift pairs in VGPRs (an opaque zero in the index: uniform loads would
-      // take 16 SGPRs per chunk, and the kernel already spills SGPRs)
-      int z0;
-      asm("v_mov_b32 %0, 0" : "=v"(z0));
-      const float* ps = pst + slice * g.CS + z0;
-      ct_f32x2 sc[CPP][4], sh[CPP][4];
-#pragma unroll
-      for (int c = 0; c < CPP; ++c)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          sc[c][q] = *(const ct_f32x2*)(ps + c * 8 + 2 * q);
-          sh[c][q] = *(const ct_f32x2*)(ps + g.C + c * 8 + 2 * q);
-        }
-      // a position's CPP chunks together (one s_pos read, one bounds test); every LDS read of a row
-      // -- its chunks and the next row's s_pos entry -- is issued before the row's writes (the
-      // compiler cannot tell the planes apart and would otherwise wait out each read alone)
-      const int NR = g.HPpad >> 6;
-      int e = s_pos[lane].y;
-      for (int r = 0; r < NR; ++r) {
-        const int p = (r << 6) + lane;
-        uint4 v[CPP];
-#pragma unroll
-        for (int c = 0; c < CPP; ++c) v[c] = *(const uint4*)(buf + c * PLANE + (r << 10));
-        const int e_next = s_pos[(r + 1 < NR ? p + 64 : p)].y;
-        const int hd = e >> 16, hh = (e >> 8) & 255, hw = e & 255;
-        const int gd = dlo + hd, gh = hlo + hh, gw = wlo + hw;
-        const bool ok = interior || ((unsigned)gd < (unsigned)g.ID && (unsigned)gh < (unsigned)g.IH &&
-                                     (unsigned)gw < (unsigned)g.IW);
-        uint4 o[CPP];
-        unsigned bits[CPP];
-#pragma unroll
-        for (int c = 0; c < CPP; ++c) {
-          o[c] = ct_bn_chunk(v[c], sc[c], sh[c], true, bits[c]);
-          if (ok) *(uint4*)(buf + c * PLANE + (r << 10)) = o[c];
-        }
-        if (writer && ok && p < HP && hd < od && hh < oh && hw < ow) {
-          const long long pos = nbase + ((long long)gd * g.IH + gh) * g.IW + gw;
-          if (pz) {
-#pragma unroll
-            for (int c = 0; c < CPP; ++c) *(uint4*)(pz + pos * g.C + slice * g.CS + c * 8) = o[c];
-          }
-          if (pmask) {                             // (CPP consecutive mask bytes, CPP-aligned)
-            unsigned char* mp = pmask + pos * (g.C >> 3) + slice * (g.CS >> 3);
-            if constexpr (CPP == 1) {
-              *mp = (unsigned char)bits[0];
-            } else if constexpr (CPP == 2) {
-              *(unsigned short*)mp = (unsigned short)(bits[0] | (bits[1] << 8));
-            } else {
-#pragma unroll
-              for (int c = 0; c < CPP; c += 4)
-                *(unsigned*)(mp + c) = bits[c] | (bits[c + 1] << 8) | (bits[c + 2] << 16) | (bits[c + 3] << 24);
-            }
-          }
-        }
-        e = e_next;
-      }
-      __builtin_amdgcn_s_setprio(0);
-    }
-  };
-
-  // DBG & 16: cycle stamps of wave 0 and the loader (barrier-A wait, job work, tile end)
+  // DBG & 16: cycle stamps of wave 0 and the loader (barrier-A wait, job work, tile end; the loader
+  // has no epilogue, so its st_e slot stays 0)
   long long st_a = 0, st_k = 0, st_e = 0, st_0 = 0, st_1 = 0;
   auto stamp = [&]() -> long long { return (DBG & 16) ? (long long)__builtin_amdgcn_s_memtime() : 0; };
   auto lap = [&](long long& acc_t) {
@@ -379,18 +270,19 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
   // whatever the order, and tiles are handed out one at a time from a counter.  With statistics
   // (stats != null) the partial sums must not depend on which workgroup ran which tiles, or the
   // statistics -- and everything downstream -- would change in the last bits run to run:
-  //   * chunk > 0 (the default): the tiles are cut into fixed CHUNKS of `chunk` consecutive
+  //   * chunk == 0 (the one-GPU default): the STATIC schedule (job k = tile k * G + slot, slots
+  //     XCD-major; one partial slab row per workgroup), the fastest when the kernel has the GPU
+  //     to itself; a CU held by another kernel delays its workgroup's whole fixed share;
+  //   * chunk > 0 (CHK instances; selected by the data-parallel GradBucketer or
+  //     FN_TILE_SCHED=chunked): the tiles are cut into fixed CHUNKS of `chunk` consecutive
   //     tiles (the host sizes them from the tile count alone, never from the grid or the CU
-  //     count); workgroups grab whole chunks from a counter, and each compute wave writes its
-  //     partial sums over a chunk into the chunk's own slab row (chunk * NCW + wave) when the
-  //     chunk's last job ends (s_job flush = the chunk id).  The sums are fixed per chunk and
-  //     the finalize adds the rows in a fixed order, so the result is the same bits whatever
-  //     the grab order -- and a workgroup that starts late (its CU held by another kernel, e.g.
-  //     an RCCL ring of the data-parallel all-reduce) simply takes fewer chunks
-  //     (profiles/r6_dp_interference.md);
-  //   * chunk == 0: the round-5 STATIC schedule (job k = tile k * G + slot, slots XCD-major;
-  //     per-workgroup partial rows), kept for the A/B of that measurement: a CU held by another
-  //     kernel there delays its workgroup's whole fixed share.
+  //     count); workgroups grab whole chunks from a counter, and when a chunk's last job ends
+  //     (s_job flush = the chunk id) each compute wave puts its partial sums over the chunk into
+  //     an LDS flush row; the loader adds the waves' rows in wave order into the chunk's one slab
+  //     row.  The sums are fixed per chunk and the finalize adds the rows in a fixed order, so
+  //     the result is the same bits whatever the grab order -- and a workgroup that starts late
+  //     (its CU held by another kernel, e.g. an RCCL ring of the data-parallel all-reduce)
+  //     simply takes fewer chunks (profiles/r6_dp_interference.md).
   const bool stat_static = stats != nullptr && (!CHK || chunk <= 0);
   const bool stat_chunk = CHK && stats != nullptr && chunk > 0;
   const int G = (int)gridDim.x;
@@ -448,179 +340,10 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
       s_job[1] = 0;
       s_job[2] = flush_of(t0, 0);
     }
-    if (WL && lane < 2 + NCW) s_job[lane == 0 ? 8 : (lane == 1 ? 9 : 10 + lane)] = 0;   // (ring counters, abort)
   }
   tile_lds_barrier();
 
-  if (WL && loader) {
-    // ================ loader wave, LDS weight ring (WL) ================
-    // The weights are one cyclic stream: job j runs slice j % nslice (a tile's jobs are its slices in
-    // order), so k-step q of the workgroup is packed row (slice (q / nks) % nslice, k-step q % nks)
-    // whatever the tiles.  Step q goes to ring slot q % wring once every compute wave has read the
-    // step wring before it (s_wdone); after its DMA has landed the loader publishes it (s_wrdy).
-    // The next job's halo rows are interleaved with the weight steps, one per step, so a wait for
-    // landed weights never waits behind a whole halo.
-    int tile = __builtin_amdgcn_readfirstlane(s_job[0]), slice = 0, t_next = -1, kjob = 1;
-    const int NR = g.HPpad >> 6;
-    const unsigned char* wsrc = reinterpret_cast<const unsigned char*>(wp) + (size_t)ct0 * 1024;
-    const unsigned ring0 = ct_lds_addr(dsm) + (unsigned)ring_off;
-    int qi = 0, wsl = 0, wk = 0, wslot = 0;      // next step to issue: its slice, k-step, ring slot
-    // (the compute waves hand slots back a whole turn -- PD k-steps -- at a time, and the loader
-    // issues and publishes whole turns: one credit poll, one wait for the landing per PD steps)
-    auto issue_w = [&]() {
-      const unsigned char* src = wsrc + ((size_t)(wsl * nks + wk) * g.nct) * 1024;
-      const unsigned dst = ring0 + (unsigned)wslot * WSLOT;
-      if (!(act & 0x800)) {                      // (0x800, timing only: no weight DMAs at all)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) ct_glds16_s(src + nt * 1024, (unsigned)lane * 16u, dst + (unsigned)nt * 1024u);
-      }
-      ++qi;
-      if (++wk == nks) {
-        wk = 0;
-        if (++wsl == nslice) wsl = 0;
-      }
-      if (++wslot == wring) wslot = 0;
-    };
-    auto credit = [&]() -> int {                 // steps the ring can hold now: the slowest reader + wring
-      if (act & 0x400) return 1 << 30;           // (timing only: no hand-off, wrong results)
-      int m = ld_cnt(s_wdone);
-#pragma unroll
-      for (int w = 1; w < NCW; ++w) m = min(m, ld_cnt(s_wdone + w));
-      return __builtin_amdgcn_readfirstlane(m) + wring;
-    };
-    auto publish = [&]() {                       // everything issued so far has landed
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) st_cnt(s_wrdy, qi);
-    };
-    // Turns stay in flight while the next one is issued: DMA instructions issued so far (nis:
-    // weights and halo rows; anything uncounted only lengthens a wait below), and for the last
-    // three issued batches the step count and nis right after them (uniform shift registers).
-    // Publishing batch b waits vmcnt(DMAs issued after it) -- the newer batches stay in flight.
-    int nis = 0, nfl = 0;                        // (nfl: batches in flight, <= 3)
-    int bq0 = 0, bq1 = 0, bq2 = 0, bn0 = 0, bn1 = 0, bn2 = 0;   // [0] = the oldest in flight
-    auto wait_vm = [&](int n) {                  // s_waitcnt vmcnt(n), n rounded down to a multiple of 4
-      switch (min(n, 60) >> 2) {
-#define CT_VMW(k) case k: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * k) : "memory"); break;
-        CT_VMW(0) CT_VMW(1) CT_VMW(2) CT_VMW(3) CT_VMW(4) CT_VMW(5) CT_VMW(6) CT_VMW(7)
-        CT_VMW(8) CT_VMW(9) CT_VMW(10) CT_VMW(11) CT_VMW(12) CT_VMW(13) CT_VMW(14)
-        default: asm volatile("s_waitcnt vmcnt(60)" ::: "memory"); break;
-#undef CT_VMW
-      }
-    };
-    auto push_batch = [&]() {                    // a batch just issued (qi, nis after it)
-      if (nfl == 0) { bq0 = qi; bn0 = nis; }
-      else if (nfl == 1) { bq1 = qi; bn1 = nis; }
-      else { bq2 = qi; bn2 = nis; }
-      ++nfl;
-    };
-    auto publish_oldest = [&]() {                // the oldest batch in flight has landed
-      wait_vm(nis - bn0);
-      if (lane == 0) st_cnt(s_wrdy, bq0);
-      bq0 = bq1; bn0 = bn1; bq1 = bq2; bn1 = bn2;
-      --nfl;
-    };
-    if (tile >= 0) {
-      dma_job(tile, 0, 0);
-      if (nslice == 1) dma_mask(tile, 0);
-      if (!stat_chunk) t_next = next_tile(kjob);
-      ++kjob;
-    }
-    while (qi < wring) issue_w();                // (credit: nothing read yet)
-    publish();
-    int par = 0, jcur = 0;
-    int fl_prev = -1;
-    int fl_cur = __builtin_amdgcn_readfirstlane(s_job[2]);
-    while (true) {
-      tile_lds_barrier();                        // A: job halo landed; the other buffer is free
-      if (fl_prev >= 0) {
-        const float* fl = s_red + (1 + (par ^ 1)) * NCW * 2 * RC;
-        float* row = stats + (long long)fl_prev * 2 * Ncol;
-        for (int i = lane; i < 2 * RC; i += 64) {
-          float v = 0.f;
-#pragma unroll
-          for (int w = 0; w < NCW; ++w) v += fl[w * 2 * RC + i];
-          const int c = ct0 * 16 + (i < RC ? i : i - RC);
-          if (c < Ncol) row[(i < RC ? 0 : Ncol) + c] = v;
-        }
-      }
-      fl_prev = fl_cur;
-      if (tile < 0) break;
-      int ntile = tile, nslc = slice + 1;
-      if (nslc == nslice) {
-        nslc = 0;
-        ntile = stat_chunk ? next_tile(kjob) : t_next;
-      }
-      fl_cur = flush_of(ntile, nslc);
-      if (lane == 0) {
-        s_job[4 * (par ^ 1)] = ntile;
-        s_job[4 * (par ^ 1) + 1] = nslc;
-        s_job[4 * (par ^ 1) + 2] = fl_cur;
-      }
-      // this period: job jcur's steps (and the compute waves' read-ahead of the next job's first)
-      // must all be issued before barrier A(jcur + 1), and the next job's first turn too, so it
-      // starts without waiting for the loader.  The next job's halo rows go in one per issued
-      // step (two when no step can be issued), and must have landed before the barrier.
-      const int qneed = (jcur + 1) * nks + 1;
-      const int qmax = qneed + wring - 1;
-      const int bo = (par ^ 1) * g.BUF;
-      int hr = ntile >= 0 ? 0 : NR;
-      if (ntile >= 0 && nslc == nslice - 1) dma_mask(ntile, par ^ 1);
-      int guard = 0;
-      while (true) {
-        const int lim = min(credit(), qmax + 1);
-        if (lim - qi >= PD || (lim > qi && lim == qmax + 1)) {   // a whole turn (or the period's rest)
-          const int n = min(lim - qi, PD);
-          for (int b = 0; b < n; ++b) {
-            issue_w();
-            nis += NT;
-            if (hr < NR) {
-              dma_job_rows(ntile, nslc, bo, hr, hr + 1);
-              nis += CPP;
-              ++hr;
-            }
-          }
-          push_batch();
-          if (nfl > 2) publish_oldest();         // (two batches stay in flight)
-          guard = 0;
-          continue;
-        }
-        if (hr < NR) {                           // no credit yet: halo rows
-          for (int b = 0; b < 2 && hr < NR; ++b) {
-            dma_job_rows(ntile, nslc, bo, hr, hr + 1);
-            nis += CPP;
-            ++hr;
-          }
-          continue;
-        }
-        if (nfl > 0) {                           // nothing to issue: the oldest batch lands
-          publish_oldest();
-          continue;
-        }
-        // the job's steps and the next job's first turn issued and landed: on to the barrier (the
-        // compute waves finish this job from the ring without the loader, and find the next one's
-        // first turn there -- no bubble at the job boundary)
-        if (qi >= qneed + PD) break;
-        // (no credit: the compute waves are behind by the whole ring.  The loop is bounded: after
-        // 2^20 empty polls -- tens of ms, far past any k-step -- it gives up and sets the abort flag
-        // that ends every wait of the workgroup, rather than hang the GPU)
-        if (++guard > (1 << 20) || ld_cnt(s_wabort)) {
-          if (lane == 0) st_cnt(s_wabort, 1);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the halo of the next job has landed)
-      if (nslc == 0 && ntile >= 0) {
-        if (!stat_chunk) t_next = next_tile(kjob);
-        ++kjob;
-      }
-      tile = ntile;
-      slice = nslc;
-      par ^= 1;
-      ++jcur;
-    }
-    tile_lds_barrier();                          // R
-  } else if (loader) {
+  if (loader) {
     // ======================= loader wave =======================
     int tile = __builtin_amdgcn_readfirstlane(s_job[0]), slice = 0, t_next = -1, kjob = 1;
     // (the chunk walk hands out the next tile only once the current one is published: t_next is
@@ -633,7 +356,6 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
       ++kjob;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (tile >= 0) xform_job(tile, 0, 0);
     int par = 0;
     int fl_prev = -1;                            // flush (chunk id) of the job before the current one
     int fl_cur = __builtin_amdgcn_readfirstlane(s_job[2]);
@@ -677,8 +399,6 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       lap(st_k);
-      if (ntile >= 0) xform_job(ntile, nslc, (par ^ 1) * g.BUF);
-      lap(st_e);                                 // (the loader's "epilogue" stamp: the BN prologue)
       tile = ntile;
       slice = nslc;
       par ^= 1;
@@ -704,9 +424,8 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
     unsigned fs[SR];
     int scl_job = 0;                             // BS: the lane's scale byte of the job's scale plane
                                                  // (less the lane's halo plane offset, see read_s)
-    // B operand: the PD-deep register ring of weight fragments streamed from global memory, or (WL)
-    // two k-steps of fragments read from the LDS weight ring one k-step ahead
-    Frag fb[WL ? 2 : PD][NT];
+    // B operand: the PD-deep register ring of weight fragments streamed from global memory
+    Frag fb[PD][NT];
     // the packed weight columns are ordered so that fragment nt row 4lg+r is output column
     // ct0*16 + 4*NT*lg + 4nt + r: a lane ends with NV = 4*NT consecutive columns of one position
     const int gc8 = ct0 * 16 + NV * lg;
@@ -794,28 +513,8 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
       for (int q = 0; q < 4; ++q) rsum[h][q] = rsq[h][q] = (ct_f32x2){0.f, 0.f};
     // ring prologue: the first job's k-steps 0..PD-1 (slice 0); every later job's come from
     // the previous job's last turn, so no job starts on an exposed L2 latency
-    if constexpr (!WL) {
 #pragma unroll
-      for (int u = 0; u < PD; ++u) load_b(reinterpret_cast<const unsigned char*>(wp) + (size_t)ct0 * FTILE, u);
-    }
-    // WL: the workgroup's k-step counter (uniform), the ring slot of the NEXT step, the published
-    // count as read during the previous step (one LDS read per step, used a step later)
-    int wq = 0, wslot1 = wring > 1 ? 1 : 0, wr_v = 0;
-    const unsigned char* rbase = dsm + ring_off + lane * 16;
-    // (bounded wait for the loader: no hang, whatever happens to it)
-    auto ring_wait = [&](int need) -> int {
-      int c = __builtin_amdgcn_readfirstlane(wr_v);
-      for (int guard = 0; c <= need; ++guard) {
-        if (guard > (1 << 20) || ld_cnt(s_wabort)) {   // (bounded: give up, and make every other
-          st_cnt(s_wabort, 1);                         //  wait of the workgroup give up at once)
-          return need + 1;
-        }
-        __builtin_amdgcn_s_sleep(1);
-        c = __builtin_amdgcn_readfirstlane(ld_cnt(s_wrdy));
-      }
-      return c;
-    };
-    bool wfirst = true;
+    for (int u = 0; u < PD; ++u) load_b(reinterpret_cast<const unsigned char*>(wp) + (size_t)ct0 * FTILE, u);
     int par = 0;
     while (true) {
       st_1 = stamp();
@@ -847,14 +546,6 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
         }
       }
       int ko_n = kofs(1);                        // offsets of the next k-step
-      if constexpr (WL) {
-        if (wfirst) {                            // (every later job's first step: read ahead by the
-          wfirst = false;                        //  previous job's last one)
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) fb[0][nt] = *(const Frag*)(rbase + nt * 1024);
-          wr_v = ld_cnt(s_wrdy);
-        }
-      }
       for (int ks = 0; ks < nks; ks += PD) {
         const unsigned char* wl = ks + PD >= nks ? wnext : wbase;   // last turn: next job's steps
 #pragma unroll
@@ -882,8 +573,7 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
                 acc[mt][nt] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb[u][nt], fa[mt], acc[mt][nt], 0, 0,
                                                                                  0, 127, 0, 127);
               else
-                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[WL ? (u & 1) : u][nt], fa[mt], acc[mt][nt],
-                                                                      0, 0, 0);
+                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[u][nt], fa[mt], acc[mt][nt], 0, 0, 0);
             }
             if constexpr (!(DBG & 2)) {
               fa[mt] = read_a(mt, ko);
@@ -892,40 +582,10 @@ __global__ __launch_bounds__(64 * (NCW + 1), 1) void conv_tile_kernel(const unsi
                 fs[r % SR] = read_s(r < MT ? r : r - MT, r < MT ? kos_c : kos_x);
               }
             }
-            if constexpr (WL) {
-              if (mt == 0) {
-                // the next k-step's fragments from the ring.  Once per turn: are the turn's reads
-                // (steps wq + 1 .. wq + PD) published?  (the count read a step ago; rarely short --
-                // then wait).  At the turn's end: this wave is done with the slots of the steps
-                // before wq + 2 (the reads, the count store and the next count read stay in order:
-                // LDS runs one wave's accesses in order; the relaxed atomics keep the compiler's)
-                int so = wslot1 * (int)WSLOT;
-                if (u == 0) {
-                  int c = __builtin_amdgcn_readfirstlane(wr_v);
-                  if (c <= wq + PD && !(act & 0x400)) c = ring_wait(wq + PD);   // (0x400: timing only)
-                  // (the slot offset through an opaque copy that takes the checked count as an
-                  // input: the turn's reads cannot be hoisted above the check)
-                  asm volatile("s_mov_b32 %0, %1" : "=s"(so) : "s"(so), "s"(c));
-                }
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) fb[(u + 1) & 1][nt] = *(const Frag*)(rbase + so + nt * 1024);
-                if (u == PD - 1) {
-                  st_cnt(s_wdone + wave, wq + 2);
-                  // (once per turn, for the next turn's check: a count read every step would be dead
-                  // until overwritten, and the overwrite waits for it -- lgkmcnt(0) every step)
-                  wr_v = ld_cnt(s_wrdy);
-                }
-              }
-            }
             if constexpr (!(DBG & 128)) __builtin_amdgcn_sched_barrier(0);   // (DBG 128: free scheduling
           }                                                                  //  within a k-step)
           // k-step ks+u+PD, or the next job's step u
-          if constexpr (WL) {
-            ++wq;
-            wslot1 = wslot1 + 1 == wring ? 0 : wslot1 + 1;
-          } else if constexpr (!(DBG & 1)) {
-            load_b(wl, u);
-          }
+          if constexpr (!(DBG & 1)) load_b(wl, u);
           if constexpr (F8 && BS) kos_c = kos_x;
           __builtin_amdgcn_sched_barrier(0);
         }
@@ -1388,7 +1048,6 @@ static int tile_chunk(const TileGeom& g) {
 
 // rows of the BN-statistics slab [rows][2][Ncol] a statistics launch writes: one per chunk (or, with
 // the static schedule, one per workgroup)
-extern "C" int fn_conv_tile_wring(const int* geom, int Ncol, int MT, int NT, int mask);
 extern "C" int fn_conv_tile_slab_rows(const int* geom, int Ncol, int NT) {
   const TileGeom g = parse_tile(geom);
   const int c = tile_chunk(g);
@@ -1399,40 +1058,24 @@ extern "C" int fn_conv_tile_slab_rows(const int* geom, int Ncol, int NT) {
 }
 
 template <int MT, int NT, int CPP, int DBG = 0, bool F8 = false, bool Q8O = false, bool I8 = false, bool BS = false,
-          int NCW = CT_NCW, bool WL = false, bool PRO = false, bool CHK = true>
+          int NCW = CT_NCW, bool CHK = true>
 static int launch_tile(dim3 grid, size_t lds, hipStream_t st, const void* s, const uint4* w, const int2* rt,
                        const int4* kt, const void* zp, const float* b, void* o, float* stats, const TileGeom& g,
                        int Ncol, int act, int* sched, long long* stamps = nullptr, const float* scale = nullptr,
                        float oscale = 0.f, const void* gmask = nullptr, const void* xsc = nullptr,
-                       void* osc = nullptr, int chunk = 0, int wring = 0, const float* pst = nullptr,
-                       void* pz = nullptr, void* pmask = nullptr, int pact = 0) {
+                       void* osc = nullptr, int chunk = 0) {
   static size_t configured = 0;
   if (lds > configured) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_tile_kernel<MT, NT, CPP, DBG, F8, Q8O, I8, BS, NCW, WL, PRO, CHK>,
+    hipError_t e = hipFuncSetAttribute((const void*)conv_tile_kernel<MT, NT, CPP, DBG, F8, Q8O, I8, BS, NCW, CHK>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
     configured = lds;
   }
-  hipLaunchKernelGGL((conv_tile_kernel<MT, NT, CPP, DBG, F8, Q8O, I8, BS, NCW, WL, PRO, CHK>), grid, dim3(64 * (NCW + 1)), lds,
+  hipLaunchKernelGGL((conv_tile_kernel<MT, NT, CPP, DBG, F8, Q8O, I8, BS, NCW, CHK>), grid, dim3(64 * (NCW + 1)), lds,
                      st, (const unsigned char*)s, w, rt, kt, (const unsigned char*)zp, b, o, stats, g, Ncol, act,
                      sched, stamps, scale, oscale, (const unsigned char*)gmask, (const unsigned*)xsc,
-                     (unsigned char*)osc, chunk, wring, pst, (bf16*)pz, (unsigned char*)pmask, pact);
+                     (unsigned char*)osc, chunk);
   return 0;
-}
-
-// The LDS weight ring (conv_tile_kernel WL): off unless FN_TILE_WLDS=1 (measured slower than the
-// register path, profiles/r6_bn_prologue.md), for the bf16 instances whose
-// plan leaves room for at least CT_WRING_MIN k-step slots (up to CT_WRING_MAX) in the 160 KiB
-#define CT_WRING_MIN 8
-#define CT_WRING_MAX 12
-static int g_tile_wlds = -1;      // -1: FN_TILE_WLDS (default off); 0 / 1 set by fn_conv_tile_set_wlds (tests)
-extern "C" void fn_conv_tile_set_wlds(int mode) { g_tile_wlds = mode < 0 ? -1 : (mode ? 1 : 0); }
-static int tile_wring(size_t lds, int NT) {
-  static const bool env_on = [] { const char* e = getenv("FN_TILE_WLDS"); return e && atoi(e) == 1; }();
-  const bool on = g_tile_wlds < 0 ? env_on : g_tile_wlds == 1;
-  if (!on || lds >= 160 * 1024) return 0;
-  const int r = (int)std::min<size_t>(CT_WRING_MAX, (160 * 1024 - lds) / ((size_t)NT * 1024));
-  return r >= CT_WRING_MIN ? r : 0;
 }
 
 // instantiations (MT, NT, CPP) -- the Python planner only emits these
@@ -1467,7 +1110,7 @@ static size_t tile_lds_total(const TileGeom& g, int MT, int NT, bool f8 = false,
 extern "C" int fn_conv_tile(const void* src, const void* wp, const void* rowtab, const void* ktab, const void* zp,
                             const float* bias, void* out, float* stats, const int* geom, int Ncol, int act, int MT,
                             int NT, int* sched, hipStream_t st, const void* bny, const float* bnp, float oscale,
-                            void* osc, const float* pst, void* pz, void* pmask, int pact) {
+                            void* osc) {
   const TileGeom g = parse_tile(geom);
   if (g.CS != 8 && g.CS != 16 && g.CS != 32 && g.CS != 64) return -2;
   const int CPP = g.CS / 8;
@@ -1503,17 +1146,9 @@ extern "C" int fn_conv_tile(const void* src, const void* wp, const void* rowtab,
   // space-to-depth stem of the fp8 inference path)
   if (!(oscale >= 0.f) || (oscale > 0.f && (stats || NT != 2 || CPP != 1))) return -2;
   if (osc && (oscale <= 0.f || Ncol > 128)) return -2;
-  // the BN prologue: a bf16 forward (no relu-mask dgrad, no fp8 output), z none / relu
-  if (pst && (bny || oscale != 0.f || osc || pact != ACT_RELU)) return -2;   // (relu only)
-  if (!pst && (pz || pmask)) return -2;
   dim3 grid((unsigned)fn_conv_tile_workers(geom, Ncol, NT), (unsigned)ncb);
   // (tests: a smaller grid must give the same bits -- only the dynamic schedules take it)
   if (g_tile_grid_cap > 0 && (!stats || tile_chunk(g) > 0)) grid.x = std::min<unsigned>(grid.x, g_tile_grid_cap);
-  const int wring = (oscale > 0.f || osc || pst) ? 0 : tile_wring(lds, NT);   // (the ring's loader: no prologue)
-  // (timing only: FN_TILE_WLDBG=1 the ring without its hand-off, 3 also without the weight DMAs)
-  static const int wl_dbg = [] { const char* e = getenv("FN_TILE_WLDBG"); return e ? atoi(e) : 0; }();
-  if (wring && (wl_dbg & 1)) act |= 0x400;
-  if (wring && (wl_dbg & 2)) act |= 0x800;
   int rc = -2;
 #ifdef FN_EXPERIMENTS
   static const int dbg = [] { const char* e = getenv("FN_TILE_DBG"); return e ? atoi(e) : 0; }();
@@ -1551,38 +1186,24 @@ extern "C" int fn_conv_tile(const void* src, const void* wp, const void* rowtab,
     return 0;
   }
 #endif  // FN_EXPERIMENTS
+// e4m3 output (oscale > 0; the Q8O instances, with block scales when osc is given), else the
+// chunked-statistics instance (CHK) or the static one
+#define CT_ARGS grid, lds, st, src, (const uint4*)wp, (const int2*)rowtab, (const int4*)ktab, zp, bias, out, stats, g, \
+                Ncol, act, sched, nullptr, nullptr
 #define CT_CASE(M, N, C)                                                                                          \
-  if (MT == M && NT == N && CPP == C)                                                                             \
-    rc = oscale > 0.f ? (osc ? launch_tile<M, N, C, 0, false, C == 1 && N == 2, false, C == 1 && N == 2>(        \
-                                   grid, lds, st, src, (const uint4*)wp, (const int2*)rowtab, (const int4*)ktab, zp,  \
-                                   bias, out, stats, g, Ncol, act, sched, nullptr, nullptr, oscale, nullptr, nullptr, \
-                                   osc)                                                                           \
-                             : launch_tile<M, N, C, 0, false, C == 1 && N == 2>(                                  \
-                                   grid, lds, st, src, (const uint4*)wp, (const int2*)rowtab, (const int4*)ktab, zp,  \
-                                   bias, out, stats, g, Ncol, act, sched, nullptr, nullptr, oscale))              \
-                      : (wring ? launch_tile<M, N, C, 0, false, false, false, false, CT_NCW, true>(                \
-                                     grid, lds + (size_t)wring * N * 1024, st, src, (const uint4*)wp,                 \
-                                     (const int2*)rowtab, (const int4*)ktab, zp, bias, out, stats, g, Ncol, act,       \
-                                     sched, nullptr, nullptr, 0.f, bny, nullptr, nullptr, stats ? tile_chunk(g) : 0,   \
-                                     wring)                                                                            \
-                               : (pst ? launch_tile<M, N, C, 0, false, false, false, false, CT_NCW, false, true>(      \
-                                            grid, lds, st, src, (const uint4*)wp, (const int2*)rowtab,                 \
-                                            (const int4*)ktab, zp, bias, out, stats, g, Ncol, act, sched, nullptr,     \
-                                            nullptr, 0.f, bny, nullptr, nullptr, stats ? tile_chunk(g) : 0, 0, pst, pz, \
-                                            pmask, pact)                                                              \
-                                      : ((stats && tile_chunk(g) > 0)                                          \
-                                             ? launch_tile<M, N, C>(grid, lds, st, src, (const uint4*)wp,              \
-                                                                    (const int2*)rowtab, (const int4*)ktab, zp, bias,  \
-                                                                    out, stats, g, Ncol, act, sched, nullptr, nullptr, \
-                                                                    0.f, bny, nullptr, nullptr, tile_chunk(g))         \
-                                             : launch_tile<M, N, C, 0, false, false, false, false, CT_NCW, false,      \
-                                                           false, false>(grid, lds, st, src, (const uint4*)wp,         \
-                                                                         (const int2*)rowtab, (const int4*)ktab, zp,   \
-                                                                         bias, out, stats, g, Ncol, act, sched,        \
-                                                                         nullptr, nullptr, 0.f, bny, nullptr,          \
-                                                                         nullptr, 0))));
+  if (MT == M && NT == N && CPP == C) {                                                                           \
+    constexpr bool Q8 = C == 1 && N == 2;                                                                         \
+    const int chunk = stats ? tile_chunk(g) : 0;                                                                  \
+    if (oscale > 0.f)                                                                                             \
+      rc = osc ? launch_tile<M, N, C, 0, false, Q8, false, Q8>(CT_ARGS, oscale, nullptr, nullptr, osc)            \
+               : launch_tile<M, N, C, 0, false, Q8>(CT_ARGS, oscale);                                             \
+    else                                                                                                          \
+      rc = chunk > 0 ? launch_tile<M, N, C>(CT_ARGS, 0.f, bny, nullptr, nullptr, chunk)                           \
+                     : launch_tile<M, N, C, 0, false, false, false, false, CT_NCW, false>(CT_ARGS, 0.f, bny);     \
+  }
   CT_INSTANCES(CT_CASE)
 #undef CT_CASE
+#undef CT_ARGS
   if (rc) return rc;
   FN_CHECK_LAUNCH();
   return 0;
@@ -1715,11 +1336,4 @@ extern "C" int fn_conv_tile_f8(const void* src, const void* wp, const void* rowt
   if (rc) return rc;
   FN_CHECK_LAUNCH();
   return 0;
-}
-
-// k-step slots of the LDS weight ring a bf16 launch of this plan gets (0: the register path) --
-// the test / profile hook for which path a layer takes
-extern "C" int fn_conv_tile_wring(const int* geom, int Ncol, int MT, int NT, int mask) {
-  const TileGeom g = parse_tile(geom);
-  return tile_wring(tile_lds_total(g, MT, NT, false, Ncol, mask != 0), NT);
 }

@@ -296,10 +296,10 @@ __global__ __launch_bounds__(wt_nthr(NW), 1) void conv_wtile_kernel(const bf16* 
 
   // BN prologue (pst != null; 16-channel slices of a plain conv, host-checked): x is the previous
   // layer's pre-BN output y and the conv's input is z = act(y * scale + shift) (pst = [scale C]
-  // [shift C]) -- the forward's conv_tile loader normalised its halos the same way and never wrote
-  // z.  Whoever DMA'd a job's x slots rewrites them in LDS once they have landed (the loader, or
-  // in the loaderless form each wave its own 1/NW), with bn_apply_kernel's fma, activation and
-  // rounding; zero-page slots (padding) stay zero.
+  // [shift C]); the matching conv_tile forward prologue was removed (profiles/r6_bn_prologue.md),
+  // so only tests reach this.  Whoever DMA'd a job's x slots rewrites them in LDS once they have
+  // landed (the loader, or in the loaderless form each wave its own 1/NW), with bn_apply_kernel's
+  // fma, activation and rounding; zero-page slots (padding) stay zero.
   // (experiment builds only: in the default instances this code raised the VGPR count and doubled
   // the SGPR spills of the weight-gradient kernels the FeatureNet-3D step runs)
   auto xform_x = [&](int tile, int bufoff, int first, int step) {
