@@ -1,4 +1,4 @@
-"""Public Python API: ``train()``, ``classify()``, ``evaluate()``, ``load()``,
+"""Public Python API: ``train()``, ``classify()``, ``segment()``, ``evaluate()``, ``load()``,
 ``save()``, ``build_model()`` and ``search()``.
 
 Reference parity: the de-facto entry point of the reference is the
@@ -190,6 +190,44 @@ def classify(model, x, batch_size: int = 256, device=None, packed_size: int | No
         probs.append(torch.softmax(fwd(prep(xt[i:i + batch_size])).float(), -1).cpu())
     p = torch.cat(probs).numpy() if probs else np.zeros((0, 0), np.float32)
     return p.argmax(-1), p
+
+
+@torch.no_grad()
+def segment(model, x, batch_size: int = 32, device=None, packed_size: int | None = None,
+            return_confidence: bool = False):
+    """Per-voxel labels of a segmentation model -> (labels uint8 [N, S, S, S], confidence float32
+    [N, S, S, S] or None).
+
+    ``model`` is a :class:`FeatureNet3DSeg` or a checkpoint path of one; ``x`` as for
+    :func:`classify`.  Runs ``FeatureNet3DSeg.predict``: the logits are never stored, and only the
+    labels (one byte per voxel) and, with ``return_confidence``, the top-1 softmax probability
+    cross to the host.  Ties go to the lowest class index.
+    """
+    if isinstance(model, (str, Path)):
+        model, _ = load(model, device)
+    if not isinstance(model, FeatureNet3DSeg):
+        raise ValueError(f"segment() takes a FeatureNet3DSeg model, not {type(model).__name__} (see classify())")
+    dev = next(model.parameters()).device
+    model.eval()
+    from .training.data import unpack_voxels
+
+    xt = torch.as_tensor(np.asarray(x)) if not isinstance(x, torch.Tensor) else x
+    labels, confs = [], []
+    for i in range(0, len(xt), batch_size):
+        xb = xt[i:i + batch_size].to(dev)
+        if packed_size is not None:
+            xb = unpack_voxels(xb, packed_size)
+        xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
+        out = model.predict(xb, want_conf=return_confidence)
+        lb, cf = out if return_confidence else (out, None)
+        labels.append(lb.cpu())
+        if cf is not None:
+            confs.append(cf.float().cpu())
+    S = model.input_size
+    lab = torch.cat(labels).numpy() if labels else np.zeros((0, S, S, S), np.uint8)
+    if not return_confidence:
+        return lab, None
+    return lab, (torch.cat(confs).numpy() if confs else np.zeros((0, S, S, S), np.float32))
 
 
 def evaluate(model, x, y, batch_size: int = 256, packed_size: int | None = None) -> float:

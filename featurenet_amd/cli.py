@@ -13,6 +13,7 @@ serve      ``ui/back/main.py`` (REST task service, port 9999)
 train      ``TensorflowGenerator(...)`` one architecture (template / product /
            featurenet3d) -> checkpoint
 classify   load a checkpoint and predict (npy / binvox folder)
+segment    per-voxel labels of a segmentation checkpoint -> .npy
 extend     ``PledgeEvolution.end2end`` (FM template -> B x C)
 sample     ``run_pledge`` (native diverse product sampler)
 template   write the built-in 1-block search-space FM
@@ -192,6 +193,28 @@ def cmd_classify(a) -> int:
     return 0
 
 
+def cmd_segment(a) -> int:
+    import numpy as np
+
+    from . import api
+
+    if os.path.isdir(a.input):
+        from .training.data import binvox_folder
+
+        x, _, _ = binvox_folder(a.input)
+        x = np.asarray(x, np.float32)[..., None]
+    else:
+        x = np.load(a.input, allow_pickle=False)
+    model, _ = api.load(a.model)
+    labels, conf = api.segment(model, x, packed_size=a.packed_size, return_confidence=bool(a.confidence))
+    np.save(a.output, labels)
+    if a.confidence:
+        np.save(a.confidence, conf)
+    counts = np.bincount(labels.reshape(-1), minlength=int(getattr(model, "num_classes", 1)))
+    print(json.dumps({"shape": list(labels.shape), "counts": counts.tolist()}))
+    return 0
+
+
 def cmd_extend(a) -> int:
     from .fm.extend import generate_featuretree
 
@@ -325,6 +348,15 @@ def build_parser() -> argparse.ArgumentParser:
                     help="FeatureNet-3D on the GPU: run in fp8, activation scales calibrated on the first N inputs "
                          "(block / per-tensor scales or bf16, as the calibration check decides)")
     cl.set_defaults(fn=cmd_classify)
+
+    sg = sub.add_parser("segment", help="per-voxel labels with a segmentation checkpoint")
+    sg.add_argument("model")
+    sg.add_argument("input", help=".npy array or a folder of .binvox files")
+    sg.add_argument("-o", "--output", required=True, help="labels, uint8 [N, S, S, S] (.npy)")
+    sg.add_argument("--confidence", default="", metavar="CONF.npy",
+                    help="also write the top-1 softmax probability per voxel (float32 .npy)")
+    sg.add_argument("--packed-size", type=int, default=None)
+    sg.set_defaults(fn=cmd_segment)
 
     e = sub.add_parser("extend", help="expand the 1-block template to B x C")
     e.add_argument("--input", default="")

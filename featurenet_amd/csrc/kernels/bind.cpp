@@ -34,6 +34,9 @@ int fn_pw_xent_blocks(long long);
 int fn_pw_fwd_xent(const void*, const void*, const float*, void*, long long, int, int, const float*, const float*, int,
                    const long long*, float*, float, float, hipStream_t);
 int fn_pw_fwd_blocks(long long, int, int);
+int fn_pw_argmax_blocks(long long, int, int);
+int fn_pw_argmax(const void*, const void*, const float*, void*, void*, long long, int, int, const float*,
+                 const float*, int, hipStream_t);
 int fn_pw_wgrad(const void*, const void*, float*, long long, int, int, hipStream_t, const float*, const float*, int,
                 float*);
 int fn_pw_wgrad_blocks(long long, int, int);
@@ -616,6 +619,20 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("dlog"), py::arg("M"), py::arg("K"), py::arg("N"),
      py::arg("psc"), py::arg("psh"), py::arg("pact"), py::arg("labels"), py::arg("xpart"), py::arg("xscale"),
      py::arg("smoothing"), py::arg("st"), py::arg("ext"));
+  // classifier head -> labels uint8 [M] (+ conf bf16 [M], 0 = not wanted); ext = {numel(x), numel(labels),
+  // numel(conf)}
+  m.def("pw_argmax_blocks", &fn_pw_argmax_blocks);
+  m.def("pw_argmax", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t labels, uintptr_t conf, long long M,
+                        int K, int N, uintptr_t psc, uintptr_t psh, int pact, uintptr_t st,
+                        std::vector<long long> ext) {
+    fits(ext, 0, M * K, "pw_argmax", "x");
+    fits(ext, 1, M, "pw_argmax", "labels");
+    if (conf) fits(ext, 2, M, "pw_argmax", "conf");
+    chk(fn_pw_argmax(P<const void*>(x), P<const void*>(w), P<const float*>(bias), P<void*>(labels), P<void*>(conf),
+                     M, K, N, P<const float*>(psc), P<const float*>(psh), pact, S(st)),
+        "pw_argmax");
+  }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("labels"), py::arg("conf"), py::arg("M"), py::arg("K"),
+     py::arg("N"), py::arg("psc"), py::arg("psh"), py::arg("pact"), py::arg("st"), py::arg("ext"));
   // part: fp32 scratch of pw_wgrad_blocks(M, K, N) x N x K floats (per-workgroup partials)
   m.def("pw_wgrad", [](uintptr_t dy, uintptr_t x, uintptr_t dw, long long M, int K, int N, uintptr_t st,
                        uintptr_t psc, uintptr_t psh, int pact, uintptr_t part, long long part_n) {

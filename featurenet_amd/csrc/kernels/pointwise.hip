@@ -280,6 +280,170 @@ __global__ __launch_bounds__(PW_NTHR, 2) void pw_fwd_kernel(const bf16* __restri
   }
 }
 
+// Classifier head for inference: labels[row] = argmax_n (X W^T + b)[row][n] (+ optionally the top-1
+// softmax probability), the per-voxel output of the segmentation model.  pw_fwd_kernel's streaming
+// structure (persistent workgroups over 256-row tiles, the next tile's 16-B loads in flight during
+// the MFMAs, weights as register B fragments, the BN + act input prologue on the chunk before the
+// LDS scatter, the same k-step order) up to the bf16 logit tile staged in LDS -- bit for bit what
+// pw_fwd_kernel<.., ACT_NONE, ..> would have stored -- then every thread takes one row: a strict
+// `>` scan from class 0 (the lowest index wins ties) and, when asked, 1 / sum exp(v - max) in fp32
+// over the bf16 logits.  The logits never reach HBM: a tile writes 256 label bytes (+ 512
+// confidence bytes) instead of 256 * N * 2.  NP: N padded to 16 / 32 / 64.
+template <int KP, int NP, bool HAS_BIAS, int PRO = -1>
+__global__ __launch_bounds__(PW_NTHR, (KP <= 32 && NP <= 32) ? 4 : 2) void pw_argmax_kernel(
+    const bf16* __restrict__ x, const bf16* __restrict__ w, const float* __restrict__ bias,
+    uint8_t* __restrict__ labels, bf16* __restrict__ conf, long long M, int K, int N,
+    const float* __restrict__ psc, const float* __restrict__ psh) {
+  constexpr int LDA = KP + 8, LDO = NP + 8;
+  constexpr int KS = KP / 32, NT = NP / 16;
+  constexpr int CH = KP / 8;                     // 16-B chunks per thread of a 256 x KP tile
+  constexpr int UR = NP >= 64 ? 2 : NP / 8;      // row scan: 16-B logit chunks in flight (VGPR budget)
+  extern __shared__ __attribute__((aligned(16))) unsigned char pw_dsm[];
+  bf16* As = reinterpret_cast<bf16*>(pw_dsm);
+  bf16* Os = As;                                 // aliased: staged only after the MFMAs have read As
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lr = lane & 15, lg = lane >> 4;
+
+  auto zero_pad = [&]() {                       // K padding of the A tile (the scatter never writes it)
+    for (int i = tid; i < PW_BM * (LDA - K); i += PW_NTHR) As[(i / (LDA - K)) * LDA + K + i % (LDA - K)] = f2bf(0.f);
+  };
+  bf16x8 fb[KS][NT];                             // weights -> B fragments (zero beyond K / N)
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const int n = nt * 16 + lr;
+      Pack8 p;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = ks * 32 + lg * 8 + j;
+        p.e[j] = (n < N && k < K) ? w[(long long)n * K + k] : f2bf(0.f);
+      }
+      fb[ks][nt] = __builtin_bit_cast(bf16x8, p.u);
+    }
+  float bv[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int n = nt * 16 + lr;
+    bv[nt] = (HAS_BIAS && n < N) ? bias[n] : 0.f;
+  }
+  // input prologue parameters: every chunk of this thread starts at channel (8 tid) mod K (host
+  // check K % 8 == 0, 2048 % K == 0, as pw_fwd_kernel), but the 8 scale / shift pairs stay in LDS
+  // and are read per tile -- 16 fewer registers live across the MFMAs and the row scan
+  __shared__ __attribute__((aligned(16))) float pss[PRO >= 0 ? 2 * KP : 4];
+  const int pk0 = PRO >= 0 ? (tid * 8) % K : 0;
+  if constexpr (PRO >= 0) {
+    if (tid < K) {
+      pss[tid] = psc[tid];
+      pss[KP + tid] = psh[tid];
+    }
+  }
+  const int ntiles = pw_tiles(M);
+  uint4 rb[CH];
+  auto load = [&](int t) {                       // tile t: 256*K contiguous bf16 (16-B aligned: 512*K*t)
+    const long long e0 = (long long)t * PW_BM * K;
+    const long long nel = (M - (long long)t * PW_BM < PW_BM ? M - (long long)t * PW_BM : PW_BM) * K;
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int c = i * PW_NTHR + tid;
+      // M % 8 == 0 (host check): every tile is a whole number of 16-B chunks
+      rb[i] = *(const uint4*)(x + e0 + (c * 8 < nel ? c * 8 : 0));
+    }
+  };
+  int t = blockIdx.x;
+  if (t < ntiles) load(t);
+  for (; t < ntiles; t += gridDim.x) {
+    const int rows = (int)(M - (long long)t * PW_BM < PW_BM ? M - (long long)t * PW_BM : PW_BM);
+    __syncthreads();                             // previous tile's Os readers are done
+    zero_pad();                                  // Os staging overwrote the padding
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {            // scatter flat chunk -> padded rows
+      const int c = i * PW_NTHR + tid;
+      if (c * 8 < rows * K) {
+        int r = (c * 8) / K, k = c * 8 - r * K;
+        if (K % 8 == 0) {                          // chunk inside one row: one 16-B LDS store
+          if constexpr (PRO >= 0) {
+            Pack8 p;
+            p.u = rb[i];
+            const float4 s0 = *(const float4*)(pss + pk0), s1 = *(const float4*)(pss + pk0 + 4);
+            const float4 h0 = *(const float4*)(pss + KP + pk0), h1 = *(const float4*)(pss + KP + pk0 + 4);
+            const float psv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+            const float phv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) p.e[j] = f2bf(act_fwd(bf2f(p.e[j]) * psv[j] + phv[j], PRO));
+            *(uint4*)(As + r * LDA + k) = p.u;
+          } else {
+            *(uint4*)(As + r * LDA + k) = rb[i];
+          }
+        } else {
+          Pack8 p;
+          p.u = rb[i];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            As[r * LDA + k] = p.e[j];
+            if (++k == K) { k = 0; ++r; }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (t + gridDim.x < ntiles) load(t + gridDim.x);   // next tile in flight during the MFMAs
+    f32x4 acc[4][NT];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int mt = 0; mt < 4; ++mt) {
+        const bf16x8 fa = *(const bf16x8*)(As + (wave * 64 + mt * 16 + lr) * LDA + ks * 32 + lg * 8);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[ks][nt], acc[mt][nt], 0, 0, 0);
+      }
+    __syncthreads();                             // all MFMA reads of As done before Os overwrites it
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          Os[(wave * 64 + mt * 16 + lg * 4 + r) * LDO + nt * 16 + lr] = f2bf(acc[mt][nt][r] + bv[nt]);
+    __syncthreads();
+    // one row per thread, 16-B LDS reads of the staged bf16 logits: a running scan, no per-class
+    // array (columns N .. NP are padding and never compete)
+    if (tid < rows) {
+      const bf16* orow = Os + tid * LDO;
+      float mx = -INFINITY;
+      int am = 0;
+#pragma unroll UR
+      for (int c8 = 0; c8 < NP / 8; ++c8) {
+        Pack8 p;
+        p.u = *(const uint4*)(orow + c8 * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float v = bf2f(p.e[j]);
+          if (c8 * 8 + j < N && v > mx) { mx = v; am = c8 * 8 + j; }
+        }
+      }
+      const long long row = (long long)t * PW_BM + tid;
+      labels[row] = (uint8_t)am;                 // 64 consecutive bytes per wave
+      if (conf) {
+        float se = 0.f;
+#pragma unroll UR
+        for (int c8 = 0; c8 < NP / 8; ++c8) {
+          Pack8 p;
+          p.u = *(const uint4*)(orow + c8 * 8);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) se += c8 * 8 + j < N ? __expf(bf2f(p.e[j]) - mx) : 0.f;
+        }
+        conf[row] = f2bf(1.f / se);
+      }
+    }
+  }
+}
+
 // dW[N][K] += sum_rows dY[row][n] * X[row][k].  Both tiles are scattered into LDS
 // TRANSPOSED ([channel][row]) so the MFMA operands (k = rows) are contiguous
 // 8-row runs; per-wave fp32 accumulators over a static (strided) tile set, added across the
@@ -557,4 +721,36 @@ extern "C" int fn_pw_wgrad(const void* dy, const void* x, float* dw, long long M
 #undef PWW
   FN_CHECK_LAUNCH();
   return fn_part_reduce(part, dw, (long long)N * K, (int)grid.x, 1, st);
+}
+
+// Classifier head -> labels (pw_argmax_kernel): x bf16 [M][K], w bf16 [N][K], labels uint8 [M], conf
+// bf16 [M] or null (the softmax pass is skipped); K, N <= 64; psc / psh / pact: the optional BN + act
+// input prologue, as fn_pw_fwd.  Grid: the 32-channel instances stay under 128 VGPRs (4 workgroups
+// per CU), the 64-wide ones take 2 -- as fn_pw_fwd.
+extern "C" int fn_pw_argmax_blocks(long long M, int K, int N) {
+  return pw_grid(M, (K <= 32 && N <= 32) ? 4 : 2);
+}
+
+extern "C" int fn_pw_argmax(const void* x, const void* w, const float* bias, void* labels, void* conf, long long M,
+                            int K, int N, const float* psc, const float* psh, int pact, hipStream_t st) {
+  if (K < 1 || K > 64 || N < 1 || N > 64 || M < 8 || M % 8 || !labels) return -2;
+  if (!pw_pro_ok(psc, psh, K) || (psc && pact != ACT_NONE && pact != ACT_RELU)) return -2;
+  const dim3 grid((unsigned)fn_pw_argmax_blocks(M, K, N));
+  const bool hb = bias != nullptr;
+#define PWM(KP, NP, HB, PA)                                                                                  \
+  hipLaunchKernelGGL((pw_argmax_kernel<KP, NP, HB, PA>), grid, dim3(PW_NTHR),                                  \
+                     (size_t)PW_BM * ((KP > NP ? KP : NP) + 8) * 2, st, (const bf16*)x, (const bf16*)w, bias,    \
+                     (uint8_t*)labels, (bf16*)conf, M, K, N, psc, psh)
+#define PWM2(KP, NP)                                                                                         \
+  do {                                                                                                       \
+    if (!psc) { if (hb) PWM(KP, NP, true, -1); else PWM(KP, NP, false, -1); }                                \
+    else if (pact == ACT_RELU) { if (hb) PWM(KP, NP, true, ACT_RELU); else PWM(KP, NP, false, ACT_RELU); }   \
+    else { if (hb) PWM(KP, NP, true, ACT_NONE); else PWM(KP, NP, false, ACT_NONE); }                         \
+  } while (0)
+  if (K <= 32) { if (N <= 16) PWM2(32, 16); else if (N <= 32) PWM2(32, 32); else PWM2(32, 64); }
+  else { if (N <= 16) PWM2(64, 16); else if (N <= 32) PWM2(64, 32); else PWM2(64, 64); }
+#undef PWM2
+#undef PWM
+  FN_CHECK_LAUNCH();
+  return 0;
 }

@@ -173,6 +173,44 @@ class FeatureNet3DSeg(nn.Module):
                                                   d.bn_momentum, d.bn_eps, d.act, stats_slab=slab)
         return h(d(x))  # [N, S, S, S, classes]
 
+    @torch.no_grad()
+    def predict(self, x: torch.Tensor, want_conf: bool = False):
+        """Per-voxel labels ``uint8 [N, S, S, S]`` (and, with ``want_conf``, the top-1 softmax
+        probability ``[N, S, S, S]``) of a model in eval mode, without the logits: on the GPU the
+        1x1 head runs in the fused head + arg-max kernel (``ops.conv.pw_argmax``) -- behind the
+        sub-pixel decoder (8 parity-class 2^3 convs, the folded BN + activation as the head's input
+        prologue) where :func:`subpixel.infer_ok`, else behind the 27-tap decoder layer; on the
+        CPU ``reference.head_argmax``.  Ties go to the lowest class index."""
+        from .. import _native
+        from ..ops import reference
+        from ..ops.conv import pw_argmax, pw_prologue_ok
+        from ..ops.spec import act_code
+
+        if self.training:
+            raise RuntimeError("FeatureNet3DSeg.predict is inference only: call model.eval() first")
+        if x.dim() == 4:
+            x = x.unsqueeze(-1)
+        z = x
+        for c in self.enc:
+            z = c(z)
+        d, h = self.dec, self.head
+        w2 = h.weight.reshape(h.cout, d.cout)
+        if not _native.use_native(z):
+            y = d(upsample2x(z))
+            labels, conf = reference.head_argmax(y, w2, h.bias)
+        elif subpixel.infer_ok(z, d.cout, z.shape[-1]) and pw_prologue_ok(d.cout):
+            y, _ = subpixel.upconv_forward(z.to(torch.bfloat16).contiguous(), d.weight)   # (BN slab: unused)
+            scale = (d.gamma * torch.rsqrt(d.running_var + d.bn_eps)).float()
+            shift = (d.beta - d.running_mean * scale).float()
+            labels, conf = pw_argmax(y.reshape(-1, d.cout), w2, h.bias,
+                                     pro=(scale.contiguous(), shift.contiguous(), act_code(d.act)),
+                                     want_conf=want_conf)
+        else:
+            y = d(upsample2x(z))
+            labels, conf = pw_argmax(y.reshape(-1, d.cout), w2, h.bias, want_conf=want_conf)
+        labels = labels.reshape(y.shape[:-1])
+        return (labels, conf.reshape(y.shape[:-1])) if want_conf else labels
+
     def loss(self, x: torch.Tensor, labels: torch.Tensor, smoothing: float = 0.0, with_correct: bool = False):
         """Mean per-voxel softmax cross-entropy against ``labels`` [N, S, S, S] (+ the number of
         top-1 hits when ``with_correct``).  Training on the GPU's sub-pixel path computes the loss

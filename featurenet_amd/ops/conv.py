@@ -815,6 +815,48 @@ def pw_prologue_ok(K: int) -> bool:
     return K % 8 == 0 and 2048 % K == 0
 
 
+def pw_argmax_ok(M: int, Kin: int, N: int, pro=None) -> bool:
+    """Shapes the fused head + arg-max kernel takes (``pw_argmax_kernel``)."""
+    return (1 <= Kin <= 64 and 1 <= N <= 64 and M >= 8 and M % 8 == 0
+            and (pro is None or pw_prologue_ok(Kin)))
+
+
+def pw_argmax(x2: torch.Tensor, w2: torch.Tensor, bias, pro=None, want_conf: bool = False):
+    """Classifier head -> labels: bf16 [M, Kin] x [Nout, Kin]^T (+bias) -> (uint8 labels [M], bf16
+    top-1 softmax probability [M] or None) without storing the logits (``pw_argmax_kernel``).
+    The label is the lowest-index arg-max of the bf16 logits :func:`pw_fwd` would store; ``pro``
+    as :func:`pw_fwd`.  Shapes the kernel does not take run :func:`pw_fwd` (or, beyond its
+    limits too, a bf16 matmul) and a torch arg-max with the same tie rule."""
+    from .reference import lowest_argmax
+
+    M, Kin = x2.shape
+    N = w2.shape[0]
+    if N > 256:
+        raise ValueError(f"pw_argmax: {N} classes do not fit a uint8 label")
+    if pw_argmax_ok(M, Kin, N, pro):
+        x2 = x2.to(torch.bfloat16).contiguous()
+        labels = torch.empty(M, dtype=torch.uint8, device=x2.device)
+        conf = torch.empty(M, dtype=torch.bfloat16, device=x2.device) if want_conf else None
+        wb = w2.detach().to(torch.bfloat16).contiguous()
+        bias = bias.detach().float().contiguous() if bias is not None else None
+        psc, psh, pact = pro if pro is not None else (None, None, 0)
+        _native.kernels().pw_argmax(x2.data_ptr(), wb.data_ptr(), _native.ptr(bias), labels.data_ptr(),
+                                    _native.ptr(conf), M, Kin, N, _native.ptr(psc), _native.ptr(psh), pact,
+                                    _native.stream(x2), [x2.numel(), labels.numel(), M if want_conf else 0])
+        return labels, conf
+    z = x2
+    if pro is not None:                          # the prologue in torch, rounded to bf16 as the kernel's A tile
+        z = x2.float() * pro[0] + pro[1]
+        z = (torch.relu(z) if pro[2] == 1 else z).to(torch.bfloat16)
+    # a 1x1x1 conv over M "samples": pw_fwd where it takes the shape, else the gather kernel
+    spec = ConvSpec.make((M, 1, 1, 1, Kin), N, 1)
+    logits = conv(z.reshape(M, 1, 1, 1, Kin), w2.detach().reshape(N, 1, 1, 1, Kin),
+                  None if bias is None else bias.detach(), spec, None).reshape(M, N)
+    lf = logits.float()
+    conf = torch.softmax(lf, -1).max(-1).values.to(torch.bfloat16) if want_conf else None
+    return lowest_argmax(lf), conf
+
+
 def pw_wgrad(dy2: torch.Tensor, x2: torch.Tensor, pro=None, out=None) -> torch.Tensor:
     """fp32 dW [Nout, Kin] = dy^T x on the pointwise kernel (``pro``: as :func:`pw_fwd`); into
     ``out`` (zeroed fp32 of N*Kin elements, e.g. the weight's flat gradient slice) when given."""

@@ -97,3 +97,32 @@ def pool(x5: torch.Tensor, spec: PoolSpec, kind: str = "max", count_pad: bool = 
 def softmax_xent(logits: torch.Tensor, labels: torch.Tensor, smoothing: float = 0.0) -> torch.Tensor:
     lg = logits if logits.dtype == torch.float64 else logits.float()   # >= fp32 (fp64 kept for gradcheck)
     return F.cross_entropy(lg, labels, label_smoothing=smoothing)
+
+
+def lowest_argmax(logits: torch.Tensor) -> torch.Tensor:
+    """uint8 arg-max over the last axis, ties to the lowest index (``torch.argmax`` leaves the
+    choice among equal maxima open)."""
+    n = logits.shape[-1]
+    idx = torch.arange(n, device=logits.device)
+    top = logits == logits.max(-1, keepdim=True).values
+    return torch.where(top, idx, n).min(-1).values.clamp_(max=n - 1).to(torch.uint8)   # (all-NaN row: n - 1)
+
+
+def head_argmax(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, pro=None):
+    """Classifier head -> per-row labels: x [..., K], w [N, K], b [N] or None ->
+    (uint8 labels [...], fp32 top-1 softmax probability [...]), in fp32.
+
+    ``pro = (scale, shift, act)``: the head reads ``act(x * scale + shift)`` (act: a name or
+    the kernels' code, none / relu).  Ties go to the lowest class index.  The oracle of the
+    ``pw_argmax`` kernel and the CPU path of ``FeatureNet3DSeg.predict``."""
+    z = x.float()
+    if pro is not None:
+        scale, shift, act = pro
+        z = z * scale.float() + shift.float()
+        if act in (1, "relu"):
+            z = F.relu(z)
+        elif act not in (0, None, "none", "linear"):
+            raise ValueError(f"head_argmax: prologue activation {act!r}")
+    logits = F.linear(z, w.float(), None if b is None else b.float())
+    conf = torch.softmax(logits, -1).max(-1).values
+    return lowest_argmax(logits), conf

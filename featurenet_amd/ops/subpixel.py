@@ -209,6 +209,21 @@ def gpu_ok(x5: torch.Tensor, K: int, C: int) -> bool:
             and conv_wtile.plan_subpixel(N, (D, H, W), C, K) is not None)
 
 
+def infer_ok(x5: torch.Tensor, K: int, C: int) -> bool:
+    """:func:`gpu_ok` for inference: only :func:`upconv_forward`'s tile plan is needed (no dgrad,
+    no weight-gradient plan).  ``FN_SUBPIXEL=0`` turns it off."""
+    import os
+
+    from .. import _native
+    from . import conv_tile
+
+    if os.environ.get("FN_SUBPIXEL", "1") == "0" or not _native.use_native(x5) or not conv_tile.enabled():
+        return False
+    N, D, H, W, Cx = x5.shape
+    return (Cx == C and K == 32 and C % 32 == 0
+            and conv_tile.plan(N, (D, H, W), (2, 2, 2), C, K) is not None)
+
+
 def upconv_forward(x5: torch.Tensor, w: torch.Tensor):
     """y = conv3^3_same(upsample2x(x)) [N, 2D, 2H, 2W, K] bf16 + its BN statistics slab, as 8
     parity-class 2^3 convs on the tile kernel writing straight into the full-res output."""
