@@ -1,5 +1,5 @@
-"""Public Python API: ``train()``, ``classify()``, ``segment()``, ``evaluate()``, ``load()``,
-``save()``, ``build_model()`` and ``search()``.
+"""Public Python API: ``train()``, ``classify()``, ``segment()``, ``evaluate()``,
+``evaluate_segmentation()``, ``load()``, ``save()``, ``build_model()`` and ``search()``.
 
 Reference parity: the de-facto entry point of the reference is the
 ``TensorflowGenerator(product, epochs, dataset, ...)`` constructor
@@ -228,6 +228,51 @@ def segment(model, x, batch_size: int = 32, device=None, packed_size: int | None
     if not return_confidence:
         return lab, None
     return lab, (torch.cat(confs).numpy() if confs else np.zeros((0, S, S, S), np.float32))
+
+
+@torch.no_grad()
+def evaluate_segmentation(model, x, y, batch_size: int = 32, device=None, packed_size: int | None = None,
+                          ignore_index: int | None = None):
+    """Score a segmentation model against true per-voxel labels -> :class:`SegScore` (confusion
+    matrix, accuracy, per-class IoU / precision / recall / dice, mIoU).
+
+    ``model`` and ``x`` as for :func:`segment`; ``y`` is ``[N, S, S, S]`` of any integer dtype with
+    values 0..255.  Voxels whose label equals ``ignore_index`` are left out.  Runs
+    ``FeatureNet3DSeg.score``: on the GPU the head counts (truth, label) pairs in its own kernel,
+    the matrix is summed over the batches on the device and crosses to the host once, at the end.
+    """
+    from .utils.segmetrics import SegScore
+
+    if isinstance(model, (str, Path)):
+        model, _ = load(model, device)
+    if not isinstance(model, FeatureNet3DSeg):
+        raise ValueError(f"evaluate_segmentation() takes a FeatureNet3DSeg model, not {type(model).__name__} "
+                         "(see evaluate())")
+    dev = next(model.parameters()).device
+    model.eval()
+    from .training.data import unpack_voxels
+
+    xt = torch.as_tensor(np.asarray(x)) if not isinstance(x, torch.Tensor) else x
+    yt = torch.as_tensor(np.asarray(y)) if not isinstance(y, torch.Tensor) else y
+    if yt.is_floating_point() or yt.dtype == torch.bool:
+        raise ValueError(f"evaluate_segmentation(): labels must be integers, not {yt.dtype}")
+    if len(yt) != len(xt):
+        raise ValueError(f"evaluate_segmentation(): {len(xt)} samples but {len(yt)} label volumes")
+    if yt.dtype != torch.uint8 and yt.numel() and not yt.is_cuda and (int(yt.min()) < 0 or int(yt.max()) > 255):
+        raise ValueError("evaluate_segmentation(): label values must lie in 0..255")
+    C = model.num_classes
+    acc = torch.zeros(C * C + 1, dtype=torch.int64, device=dev)
+    for i in range(0, len(xt), batch_size):
+        xb = xt[i:i + batch_size].to(dev)
+        if packed_size is not None:
+            xb = unpack_voxels(xb, packed_size)
+        xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
+        acc, _ = model.score(xb, yt[i:i + batch_size].to(dev).to(torch.uint8), ignore_index=ignore_index, acc=acc)
+    counts = acc.cpu().numpy()
+    if counts[-1]:
+        raise ValueError(f"evaluate_segmentation(): {int(counts[-1])} voxels carry a label >= {C} (the model's "
+                         "class count); pass ignore_index to mask unlabelled voxels")
+    return SegScore.from_confusion(counts[:-1].reshape(C, C))
 
 
 def evaluate(model, x, y, batch_size: int = 256, packed_size: int | None = None) -> float:

@@ -14,6 +14,7 @@ train      ``TensorflowGenerator(...)`` one architecture (template / product /
            featurenet3d) -> checkpoint
 classify   load a checkpoint and predict (npy / binvox folder)
 segment    per-voxel labels of a segmentation checkpoint -> .npy
+score      confusion matrix / per-class IoU / mIoU of a segmentation checkpoint against true labels
 extend     ``PledgeEvolution.end2end`` (FM template -> B x C)
 sample     ``run_pledge`` (native diverse product sampler)
 template   write the built-in 1-block search-space FM
@@ -215,6 +216,22 @@ def cmd_segment(a) -> int:
     return 0
 
 
+def cmd_score(a) -> int:
+    import numpy as np
+
+    from . import api
+
+    x = np.load(a.input, allow_pickle=False)
+    y = np.load(a.truth, allow_pickle=False)
+    score = api.evaluate_segmentation(a.model, x, y, packed_size=a.packed_size, ignore_index=a.ignore_index)
+    summary = json.dumps(score.to_dict())
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(summary + "\n")
+    print(summary)
+    return 0
+
+
 def cmd_extend(a) -> int:
     from .fm.extend import generate_featuretree
 
@@ -357,6 +374,15 @@ def build_parser() -> argparse.ArgumentParser:
                     help="also write the top-1 softmax probability per voxel (float32 .npy)")
     sg.add_argument("--packed-size", type=int, default=None)
     sg.set_defaults(fn=cmd_segment)
+
+    sc = sub.add_parser("score", help="confusion matrix, per-class IoU and mIoU of a segmentation checkpoint")
+    sc.add_argument("model")
+    sc.add_argument("input", help="voxels (.npy), as for segment")
+    sc.add_argument("truth", help="true labels, integer [N, S, S, S] (.npy)")
+    sc.add_argument("--ignore-index", type=int, default=None, metavar="K", help="label value of unlabelled voxels")
+    sc.add_argument("--packed-size", type=int, default=None)
+    sc.add_argument("--json", default="", metavar="OUT", help="also write the summary to this file")
+    sc.set_defaults(fn=cmd_score)
 
     e = sub.add_parser("extend", help="expand the 1-block template to B x C")
     e.add_argument("--input", default="")

@@ -37,6 +37,9 @@ int fn_pw_fwd_blocks(long long, int, int);
 int fn_pw_argmax_blocks(long long, int, int);
 int fn_pw_argmax(const void*, const void*, const float*, void*, void*, long long, int, int, const float*,
                  const float*, int, hipStream_t);
+int fn_pw_argmax_cm_blocks(long long, int, int);
+int fn_pw_argmax_cm(const void*, const void*, const float*, const void*, void*, void*, void*, long long, int, int, int,
+                    const float*, const float*, int, hipStream_t);
 int fn_pw_wgrad(const void*, const void*, float*, long long, int, int, hipStream_t, const float*, const float*, int,
                 float*);
 int fn_pw_wgrad_blocks(long long, int, int);
@@ -633,6 +636,26 @@ PYBIND11_MODULE(_C, m) {
         "pw_argmax");
   }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("labels"), py::arg("conf"), py::arg("M"), py::arg("K"),
      py::arg("N"), py::arg("psc"), py::arg("psh"), py::arg("pact"), py::arg("st"), py::arg("ext"));
+  // classifier head -> confusion matrix: acc int64 [N*N + 1] += counts of (truth, arg-max) over the M rows
+  // (slot N*N: truth >= N; truth == ignore is skipped, -1 = none); labels uint8 [M] or 0 = not wanted; part:
+  // uint32 scratch [pw_argmax_cm_blocks(M, K, N)][N*N + 1]; ext = {numel(x), numel(truth), numel(labels),
+  // numel(part), numel(acc)}
+  m.def("pw_argmax_cm_blocks", &fn_pw_argmax_cm_blocks);
+  m.def("pw_argmax_cm", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t truth, uintptr_t labels, uintptr_t part,
+                           uintptr_t acc, long long M, int K, int N, int ignore, uintptr_t psc, uintptr_t psh, int pact,
+                           uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, M * K, "pw_argmax_cm", "x");
+    fits(ext, 1, M, "pw_argmax_cm", "truth");
+    if (labels) fits(ext, 2, M, "pw_argmax_cm", "labels");
+    fits(ext, 4, (long long)N * N + 1, "pw_argmax_cm", "acc");
+    fits(ext, 3, (long long)fn_pw_argmax_cm_blocks(M, K, N) * ((long long)N * N + 1), "pw_argmax_cm", "part");
+    chk(fn_pw_argmax_cm(P<const void*>(x), P<const void*>(w), P<const float*>(bias), P<const void*>(truth),
+                        P<void*>(labels), P<void*>(part), P<void*>(acc), M, K, N, ignore, P<const float*>(psc),
+                        P<const float*>(psh), pact, S(st)),
+        "pw_argmax_cm");
+  }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("truth"), py::arg("labels"), py::arg("part"), py::arg("acc"),
+     py::arg("M"), py::arg("K"), py::arg("N"), py::arg("ignore"), py::arg("psc"), py::arg("psh"), py::arg("pact"),
+     py::arg("st"), py::arg("ext"));
   // part: fp32 scratch of pw_wgrad_blocks(M, K, N) x N x K floats (per-workgroup partials)
   m.def("pw_wgrad", [](uintptr_t dy, uintptr_t x, uintptr_t dw, long long M, int K, int N, uintptr_t st,
                        uintptr_t psc, uintptr_t psh, int pact, uintptr_t part, long long part_n) {

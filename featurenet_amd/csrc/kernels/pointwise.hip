@@ -289,11 +289,19 @@ __global__ __launch_bounds__(PW_NTHR, 2) void pw_fwd_kernel(const bf16* __restri
 // `>` scan from class 0 (the lowest index wins ties) and, when asked, 1 / sum exp(v - max) in fp32
 // over the bf16 logits.  The logits never reach HBM: a tile writes 256 label bytes (+ 512
 // confidence bytes) instead of 256 * N * 2.  NP: N padded to 16 / 32 / 64.
-template <int KP, int NP, bool HAS_BIAS, int PRO = -1>
+//
+// CM (the scorer): the row's arg-max is not (only) stored but counted against truth[row] in a
+// per-workgroup confusion histogram hist[N*N + 1] (uint32, in the dynamic LDS behind the tile):
+// hist[t * N + am] for t < N, the out-of-range slot hist[N*N] for t >= N, nothing for t == ignore.
+// Integer LDS adds only; after its last tile the workgroup stores the whole histogram to its row of
+// `part` (every launched workgroup writes every slot: no memset, replayable), summed over the
+// workgroups by cm_accumulate_kernel.  `labels` may be null (nothing written per row); no conf.
+template <int KP, int NP, bool HAS_BIAS, int PRO = -1, bool CM = false>
 __global__ __launch_bounds__(PW_NTHR, (KP <= 32 && NP <= 32) ? 4 : 2) void pw_argmax_kernel(
     const bf16* __restrict__ x, const bf16* __restrict__ w, const float* __restrict__ bias,
     uint8_t* __restrict__ labels, bf16* __restrict__ conf, long long M, int K, int N,
-    const float* __restrict__ psc, const float* __restrict__ psh) {
+    const float* __restrict__ psc, const float* __restrict__ psh, const uint8_t* __restrict__ truth = nullptr,
+    uint32_t* __restrict__ part = nullptr, int ignore = -1) {
   constexpr int LDA = KP + 8, LDO = NP + 8;
   constexpr int KS = KP / 32, NT = NP / 16;
   constexpr int CH = KP / 8;                     // 16-B chunks per thread of a 256 x KP tile
@@ -338,6 +346,10 @@ __global__ __launch_bounds__(PW_NTHR, (KP <= 32 && NP <= 32) ? 4 : 2) void pw_ar
       pss[KP + tid] = psh[tid];
     }
   }
+  // CM: the workgroup's histogram, zeroed once (the tile loop's barriers order it before the adds)
+  uint32_t* hist = reinterpret_cast<uint32_t*>(pw_dsm + (size_t)PW_BM * ((KP > NP ? KP : NP) + 8) * 2);
+  if constexpr (CM)
+    for (int i = tid; i <= N * N; i += PW_NTHR) hist[i] = 0u;
   const int ntiles = pw_tiles(M);
   uint4 rb[CH];
   auto load = [&](int t) {                       // tile t: 256*K contiguous bf16 (16-B aligned: 512*K*t)
@@ -428,8 +440,15 @@ __global__ __launch_bounds__(PW_NTHR, (KP <= 32 && NP <= 32) ? 4 : 2) void pw_ar
         }
       }
       const long long row = (long long)t * PW_BM + tid;
-      labels[row] = (uint8_t)am;                 // 64 consecutive bytes per wave
-      if (conf) {
+      if (!CM || labels) labels[row] = (uint8_t)am;   // 64 consecutive bytes per wave
+      if constexpr (CM) {
+        // one integer LDS add per row.  Combining equal keys across the wave first (ballot + one add
+        // of the popcount) measured the same on an all-one-bin input and 1.1-2x slower on mixed ones
+        // (profiles/segment_score.md), so the plain add stays.
+        const int tr = truth[row];
+        if (tr != ignore) atomicAdd(&hist[tr >= N ? N * N : tr * N + am], 1u);
+      }
+      if (conf) {                                // (null in the CM instances)
         float se = 0.f;
 #pragma unroll UR
         for (int c8 = 0; c8 < NP / 8; ++c8) {
@@ -442,6 +461,30 @@ __global__ __launch_bounds__(PW_NTHR, (KP <= 32 && NP <= 32) ? 4 : 2) void pw_ar
       }
     }
   }
+  if constexpr (CM) {
+    __syncthreads();
+    uint32_t* prow = part + (size_t)blockIdx.x * (size_t)(N * N + 1);
+    for (int i = tid; i <= N * N; i += PW_NTHR) prow[i] = hist[i];
+  }
+}
+
+// acc[i] += sum_b part[b][i] (b in order), i < len: the per-workgroup confusion histograms of one
+// pw_argmax_kernel<.., CM> launch into the caller's int64 running matrix.  One thread per slot.
+__global__ __launch_bounds__(256) void cm_accumulate_kernel(const uint32_t* __restrict__ part,
+                                                            long long* __restrict__ acc, int len, int nb) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  long long s = 0;
+  int b = 0;
+  for (; b + 32 <= nb; b += 32) {               // 32 independent loads in flight, added in order
+    uint32_t v[32];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) v[j] = part[(size_t)(b + j) * len + i];
+#pragma unroll
+    for (int j = 0; j < 32; ++j) s += v[j];
+  }
+  for (; b < nb; ++b) s += part[(size_t)b * len + i];
+  acc[i] += s;
 }
 
 // dW[N][K] += sum_rows dY[row][n] * X[row][k].  Both tiles are scattered into LDS
@@ -751,6 +794,44 @@ extern "C" int fn_pw_argmax(const void* x, const void* w, const float* bias, voi
   else { if (N <= 16) PWM2(64, 16); else if (N <= 32) PWM2(64, 32); else PWM2(64, 64); }
 #undef PWM2
 #undef PWM
+  FN_CHECK_LAUNCH();
+  return 0;
+}
+
+// Classifier head -> confusion matrix (pw_argmax_kernel<.., CM> + cm_accumulate_kernel): operands as
+// fn_pw_argmax, plus truth uint8 [M]; rows whose truth == ignore (-1: none) are skipped.  labels
+// uint8 [M] or null (nothing is written per row).  part: uint32 scratch [fn_pw_argmax_cm_blocks]
+// [N*N + 1], fully rewritten by every launch; acc: int64 [N*N + 1], ADDED to (rows = truth, columns =
+// prediction, slot N*N = rows whose truth is >= N).  M < 2^32: a workgroup's uint32 counters cannot wrap.
+extern "C" int fn_pw_argmax_cm_blocks(long long M, int K, int N) { return fn_pw_argmax_blocks(M, K, N); }
+
+extern "C" int fn_pw_argmax_cm(const void* x, const void* w, const float* bias, const void* truth, void* labels,
+                               void* part, void* acc, long long M, int K, int N, int ignore, const float* psc,
+                               const float* psh, int pact, hipStream_t st) {
+  if (K < 1 || K > 64 || N < 1 || N > 64 || M < 8 || M % 8 || M >= (1LL << 32)) return -2;
+  if (!truth || !part || !acc || ignore < -1 || ignore > 255) return -2;
+  if (!pw_pro_ok(psc, psh, K) || (psc && pact != ACT_NONE && pact != ACT_RELU)) return -2;
+  const int nb = fn_pw_argmax_cm_blocks(M, K, N), len = N * N + 1;
+  const dim3 grid((unsigned)nb);
+  const bool hb = bias != nullptr;
+#define PWC(KP, NP, HB, PA)                                                                                  \
+  hipLaunchKernelGGL((pw_argmax_kernel<KP, NP, HB, PA, true>), grid, dim3(PW_NTHR),                            \
+                     (size_t)PW_BM * ((KP > NP ? KP : NP) + 8) * 2 + (size_t)len * 4, st, (const bf16*)x,        \
+                     (const bf16*)w, bias, (uint8_t*)labels, (bf16*)nullptr, M, K, N, psc, psh,                  \
+                     (const uint8_t*)truth, (uint32_t*)part, ignore)
+#define PWC2(KP, NP)                                                                                         \
+  do {                                                                                                       \
+    if (!psc) { if (hb) PWC(KP, NP, true, -1); else PWC(KP, NP, false, -1); }                                \
+    else if (pact == ACT_RELU) { if (hb) PWC(KP, NP, true, ACT_RELU); else PWC(KP, NP, false, ACT_RELU); }   \
+    else { if (hb) PWC(KP, NP, true, ACT_NONE); else PWC(KP, NP, false, ACT_NONE); }                         \
+  } while (0)
+  if (K <= 32) { if (N <= 16) PWC2(32, 16); else if (N <= 32) PWC2(32, 32); else PWC2(32, 64); }
+  else { if (N <= 16) PWC2(64, 16); else if (N <= 32) PWC2(64, 32); else PWC2(64, 64); }
+#undef PWC2
+#undef PWC
+  FN_CHECK_LAUNCH();
+  hipLaunchKernelGGL(cm_accumulate_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st,
+                     (const uint32_t*)part, (long long*)acc, len, nb);
   FN_CHECK_LAUNCH();
   return 0;
 }

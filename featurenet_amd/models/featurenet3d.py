@@ -173,21 +173,17 @@ class FeatureNet3DSeg(nn.Module):
                                                   d.bn_momentum, d.bn_eps, d.act, stats_slab=slab)
         return h(d(x))  # [N, S, S, S, classes]
 
-    @torch.no_grad()
-    def predict(self, x: torch.Tensor, want_conf: bool = False):
-        """Per-voxel labels ``uint8 [N, S, S, S]`` (and, with ``want_conf``, the top-1 softmax
-        probability ``[N, S, S, S]``) of a model in eval mode, without the logits: on the GPU the
-        1x1 head runs in the fused head + arg-max kernel (``ops.conv.pw_argmax``) -- behind the
-        sub-pixel decoder (8 parity-class 2^3 convs, the folded BN + activation as the head's input
-        prologue) where :func:`subpixel.infer_ok`, else behind the 27-tap decoder layer; on the
-        CPU ``reference.head_argmax``.  Ties go to the lowest class index."""
+    def _head_operands(self, x: torch.Tensor):
+        """Eval-mode trunk shared by :meth:`predict` and :meth:`score` -> ``(y, w2, pro, native)``:
+        the 1x1 head's input ``y [N, S, S, S, C]``, its weight as ``[classes, C]``, the input
+        prologue ``(scale, shift, act)`` or None, and whether the native head kernels run.  On the
+        GPU the decoder is the sub-pixel one (8 parity-class 2^3 convs, its folded BN + activation
+        left to the head's prologue) where :func:`subpixel.infer_ok`, else the 27-tap layer; on
+        the CPU the reference layer."""
         from .. import _native
-        from ..ops import reference
-        from ..ops.conv import pw_argmax, pw_prologue_ok
+        from ..ops.conv import pw_prologue_ok
         from ..ops.spec import act_code
 
-        if self.training:
-            raise RuntimeError("FeatureNet3DSeg.predict is inference only: call model.eval() first")
         if x.dim() == 4:
             x = x.unsqueeze(-1)
         z = x
@@ -196,20 +192,71 @@ class FeatureNet3DSeg(nn.Module):
         d, h = self.dec, self.head
         w2 = h.weight.reshape(h.cout, d.cout)
         if not _native.use_native(z):
-            y = d(upsample2x(z))
-            labels, conf = reference.head_argmax(y, w2, h.bias)
-        elif subpixel.infer_ok(z, d.cout, z.shape[-1]) and pw_prologue_ok(d.cout):
+            return d(upsample2x(z)), w2, None, False
+        if subpixel.infer_ok(z, d.cout, z.shape[-1]) and pw_prologue_ok(d.cout):
             y, _ = subpixel.upconv_forward(z.to(torch.bfloat16).contiguous(), d.weight)   # (BN slab: unused)
             scale = (d.gamma * torch.rsqrt(d.running_var + d.bn_eps)).float()
             shift = (d.beta - d.running_mean * scale).float()
-            labels, conf = pw_argmax(y.reshape(-1, d.cout), w2, h.bias,
-                                     pro=(scale.contiguous(), shift.contiguous(), act_code(d.act)),
-                                     want_conf=want_conf)
+            return y, w2, (scale.contiguous(), shift.contiguous(), act_code(d.act)), True
+        return d(upsample2x(z)), w2, None, True
+
+    @torch.no_grad()
+    def predict(self, x: torch.Tensor, want_conf: bool = False):
+        """Per-voxel labels ``uint8 [N, S, S, S]`` (and, with ``want_conf``, the top-1 softmax
+        probability ``[N, S, S, S]``) of a model in eval mode, without the logits: on the GPU the
+        1x1 head runs in the fused head + arg-max kernel (``ops.conv.pw_argmax``) -- behind the
+        sub-pixel decoder (8 parity-class 2^3 convs, the folded BN + activation as the head's input
+        prologue) where :func:`subpixel.infer_ok`, else behind the 27-tap decoder layer; on the
+        CPU ``reference.head_argmax``.  Ties go to the lowest class index."""
+        from ..ops import reference
+        from ..ops.conv import pw_argmax
+
+        if self.training:
+            raise RuntimeError("FeatureNet3DSeg.predict is inference only: call model.eval() first")
+        y, w2, pro, native = self._head_operands(x)
+        if not native:
+            labels, conf = reference.head_argmax(y, w2, self.head.bias)
         else:
-            y = d(upsample2x(z))
-            labels, conf = pw_argmax(y.reshape(-1, d.cout), w2, h.bias, want_conf=want_conf)
+            labels, conf = pw_argmax(y.reshape(-1, y.shape[-1]), w2, self.head.bias, pro=pro, want_conf=want_conf)
         labels = labels.reshape(y.shape[:-1])
         return (labels, conf.reshape(y.shape[:-1])) if want_conf else labels
+
+    @torch.no_grad()
+    def score(self, x: torch.Tensor, y: torch.Tensor, ignore_index: int | None = None,
+              acc: torch.Tensor | None = None, want_labels: bool = False):
+        """Confusion counts of :meth:`predict`'s labels against the true labels ``y [N, S, S, S]``
+        (any integer dtype, values 0..255) of a model in eval mode -> ``(acc, labels or None)``:
+        ``acc`` int64 ``[C*C + 1]`` on the model's device, ``acc[t*C + p]`` = voxels with truth
+        ``t`` labelled ``p``, ``acc[C*C]`` = voxels whose truth is ``>= C``; voxels with
+        ``y == ignore_index`` are counted nowhere.  ``acc`` is added to when given (sum over
+        batches on the device, copy once).  Same decoder dispatch as :meth:`predict`; on the GPU
+        the head counts in its own kernel (``ops.conv.pw_argmax_score``) and writes nothing per
+        voxel unless ``want_labels``."""
+        from ..ops import reference
+        from ..ops.conv import pw_argmax_score
+
+        if self.training:
+            raise RuntimeError("FeatureNet3DSeg.score is inference only: call model.eval() first")
+        if y.is_floating_point() or y.dtype == torch.bool:
+            raise ValueError(f"score: labels must be an integer tensor, not {y.dtype}")
+        yv, w2, pro, native = self._head_operands(x)
+        if y.numel() != yv.numel() // yv.shape[-1]:
+            raise ValueError(f"score: labels {tuple(y.shape)} do not match the output grid {tuple(yv.shape[:-1])}")
+        if y.dtype != torch.uint8:
+            if not y.is_cuda and y.numel() and (int(y.min()) < 0 or int(y.max()) > 255):
+                raise ValueError("score: label values must lie in 0..255")
+            y = y.to(yv.device).to(torch.uint8)
+        y = y.to(yv.device)
+        C = self.head.cout
+        if not native:
+            labels, _ = reference.head_argmax(yv, w2, self.head.bias)
+            cm = reference.confusion(y, labels, C, ignore_index)
+            acc = cm if acc is None else acc.add_(cm)
+            labels = labels if want_labels else None
+        else:
+            acc, labels = pw_argmax_score(yv.reshape(-1, yv.shape[-1]), w2, self.head.bias, y, pro=pro,
+                                          ignore_index=ignore_index, acc=acc, want_labels=want_labels)
+        return acc, (labels.reshape(yv.shape[:-1]) if labels is not None else None)
 
     def loss(self, x: torch.Tensor, labels: torch.Tensor, smoothing: float = 0.0, with_correct: bool = False):
         """Mean per-voxel softmax cross-entropy against ``labels`` [N, S, S, S] (+ the number of

@@ -857,6 +857,45 @@ def pw_argmax(x2: torch.Tensor, w2: torch.Tensor, bias, pro=None, want_conf: boo
     return lowest_argmax(lf), conf
 
 
+def pw_argmax_score(x2: torch.Tensor, w2: torch.Tensor, bias, truth: torch.Tensor, pro=None,
+                    ignore_index: int | None = None, acc: torch.Tensor | None = None, want_labels: bool = False):
+    """Classifier head -> confusion matrix: the labels of :func:`pw_argmax` counted against
+    ``truth`` (integer [M], values 0..255) without being stored -> (``acc`` int64 [N*N + 1], uint8
+    labels [M] or None).  ``acc[t*N + p]`` counts rows with truth ``t`` and label ``p``, ``acc[N*N]``
+    rows whose truth is ``>= N``; rows with ``truth == ignore_index`` count nowhere
+    (``reference.confusion``).  ``acc`` is allocated zeroed when none is given, else added to, so a
+    caller sums over batches on the device.  One head launch with a per-workgroup LDS histogram
+    (``pw_argmax_kernel<.., CM>``) plus ``cm_accumulate_kernel``; shapes the kernel does not take
+    run :func:`pw_argmax` and ``reference.confusion`` on the device."""
+    from .reference import confusion
+
+    M, Kin = x2.shape
+    N = w2.shape[0]
+    if truth.numel() != M:
+        raise ValueError(f"pw_argmax_score: truth has {truth.numel()} elements for {M} rows")
+    if acc is None:
+        acc = torch.zeros(N * N + 1, dtype=torch.int64, device=x2.device)
+    elif acc.dtype != torch.int64 or acc.numel() != N * N + 1 or not acc.is_contiguous():
+        raise ValueError(f"pw_argmax_score: acc must be a contiguous int64 tensor of {N * N + 1} elements")
+    if not (pw_argmax_ok(M, Kin, N, pro) and M < 1 << 32):
+        labels, _ = pw_argmax(x2, w2, bias, pro=pro)
+        acc += confusion(truth.reshape(-1).to(labels.device), labels, N, ignore_index)
+        return acc, (labels if want_labels else None)
+    x2 = x2.to(torch.bfloat16).contiguous()
+    truth = truth.reshape(-1).to(torch.uint8).contiguous()
+    labels = torch.empty(M, dtype=torch.uint8, device=x2.device) if want_labels else None
+    wb = w2.detach().to(torch.bfloat16).contiguous()
+    bias = bias.detach().float().contiguous() if bias is not None else None
+    psc, psh, pact = pro if pro is not None else (None, None, 0)
+    ignore = -1 if ignore_index is None or not 0 <= int(ignore_index) <= 255 else int(ignore_index)
+    K_ = _native.kernels()
+    part = torch.empty(int(K_.pw_argmax_cm_blocks(M, Kin, N)) * (N * N + 1), dtype=torch.int32, device=x2.device)
+    K_.pw_argmax_cm(x2.data_ptr(), wb.data_ptr(), _native.ptr(bias), truth.data_ptr(), _native.ptr(labels),
+                    part.data_ptr(), acc.data_ptr(), M, Kin, N, ignore, _native.ptr(psc), _native.ptr(psh), pact,
+                    _native.stream(x2), [x2.numel(), truth.numel(), M if want_labels else 0, part.numel(), acc.numel()])
+    return acc, labels
+
+
 def pw_wgrad(dy2: torch.Tensor, x2: torch.Tensor, pro=None, out=None) -> torch.Tensor:
     """fp32 dW [Nout, Kin] = dy^T x on the pointwise kernel (``pro``: as :func:`pw_fwd`); into
     ``out`` (zeroed fp32 of N*Kin elements, e.g. the weight's flat gradient slice) when given."""

@@ -126,3 +126,20 @@ def head_argmax(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor | None, pro=No
     logits = F.linear(z, w.float(), None if b is None else b.float())
     conf = torch.softmax(logits, -1).max(-1).values
     return lowest_argmax(logits), conf
+
+
+def confusion(truth: torch.Tensor, pred: torch.Tensor, n_classes: int, ignore_index: int | None = None) -> torch.Tensor:
+    """Confusion counts of ``pred`` against ``truth`` (integer tensors of one shape) -> int64
+    ``[n*n + 1]``: slot ``t*n + p`` counts the elements with truth ``t < n`` and prediction ``p``
+    (rows = truth, columns = prediction), the last slot those whose truth is ``>= n`` (out of
+    range); elements whose truth equals ``ignore_index`` are counted nowhere.  Exact integers:
+    the oracle of the scoring kernel (``pw_argmax_cm``) and the CPU path of
+    ``FeatureNet3DSeg.score``."""
+    n = int(n_classes)
+    t = truth.reshape(-1).to(torch.int64)
+    p = pred.reshape(-1).to(torch.int64)
+    if ignore_index is not None:
+        keep = t != int(ignore_index)
+        t, p = t[keep], p[keep]
+    key = torch.where(t >= n, torch.full_like(t, n * n), t * n + p)
+    return torch.bincount(key, minlength=n * n + 1)
