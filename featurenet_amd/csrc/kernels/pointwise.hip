@@ -18,11 +18,141 @@
 // combination projection (model/operation.py:179-186).
 #include "common.h"
 
+#include <type_traits>
+
 #define PW_BM 256
 #define PW_NTHR 256
 
-
 __device__ __forceinline__ int pw_tiles(long long M) { return (int)((M + PW_BM - 1) / PW_BM); }
+__device__ __forceinline__ int pw_rows(long long M, int t) {   // rows of tile t (the last may be ragged)
+  return (int)(M - (long long)t * PW_BM < PW_BM ? M - (long long)t * PW_BM : PW_BM);
+}
+
+// dynamic LDS bytes: the A tile / output staging region of pw_fwd_kernel and pw_argmax_kernel, and
+// the two transposed tiles of pw_wgrad_kernel
+constexpr size_t pw_tile_lds(int KP, int NP) { return (size_t)PW_BM * ((KP > NP ? KP : NP) + 8) * 2; }
+constexpr size_t pw_wgrad_lds(int KP, int NP) { return (size_t)(KP + NP) * (PW_BM + 8) * 2; }
+
+// ---- The streaming front half, shared by pw_fwd_kernel and pw_argmax_kernel (the tile load by
+// pw_wgrad_kernel too): one 256-row tile of X through LDS and the MFMAs to the bf16 output tile
+// staged in LDS.  The A tile [256][KP+8] and the output staging [256][NP+8] (bf16) alias one
+// dynamic LDS region.
+
+// weights -> B fragments (k rows beyond K and n cols beyond N are zero) and the bias registers
+template <int KS, int NT, bool HAS_BIAS>
+__device__ __forceinline__ void pw_weights(const bf16* __restrict__ w, const float* __restrict__ bias, int K, int N,
+                                           bf16x8 (&fb)[KS][NT], float (&bv)[NT]) {
+  const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, lg = lane >> 4;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      const int n = nt * 16 + lr;
+      Pack8 p;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = ks * 32 + lg * 8 + j;
+        p.e[j] = (n < N && k < K) ? w[(long long)n * K + k] : f2bf(0.f);
+      }
+      fb[ks][nt] = __builtin_bit_cast(bf16x8, p.u);
+    }
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int n = nt * 16 + lr;
+    bv[nt] = (HAS_BIAS && n < N) ? bias[n] : 0.f;
+  }
+}
+
+// tile t of a channels-last [M][C] tensor: 256*C contiguous bf16 (16-B aligned: 512*C*t), CH 16-B
+// chunks per thread; the chunks past the end of a ragged tile re-read chunk 0
+template <int CH>
+__device__ __forceinline__ void pw_load(const bf16* __restrict__ src, long long M, int C, int t, uint4 (&rb)[CH]) {
+  const long long e0 = (long long)t * PW_BM * C;
+  const long long nel = (M - (long long)t * PW_BM < PW_BM ? M - (long long)t * PW_BM : PW_BM) * C;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < CH; ++i) {
+    const int c = i * PW_NTHR + tid;
+    // M % 8 == 0 (host check): every tile is a whole number of 16-B chunks
+    rb[i] = *(const uint4*)(src + e0 + (c * 8 < nel ? c * 8 : 0));
+  }
+}
+
+// flat chunks -> padded rows of As, after zeroing its K padding (the scatter never writes it, the
+// output staging does).  PRO >= 0: the input prologue x <- act(x * psv[j] + phv[j]) on the chunk (a
+// BatchNorm + activation whose normalised output is never written): with K % 8 == 0 and
+// 2048 % K == 0 (host check) every chunk this thread loads starts at channel (8 tid) mod K, so 8
+// scale / shift pairs cover all of them; pro(psv, phv) hands them over, from wherever the kernel
+// keeps them
+template <int KP, int PRO, class ProFn>
+__device__ __forceinline__ void pw_scatter(bf16* As, const uint4 (&rb)[KP / 8], int rows, int K, ProFn pro) {
+  constexpr int LDA = KP + 8;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < PW_BM * (LDA - K); i += PW_NTHR) As[(i / (LDA - K)) * LDA + K + i % (LDA - K)] = f2bf(0.f);
+#pragma unroll
+  for (int i = 0; i < KP / 8; ++i) {
+    const int c = i * PW_NTHR + tid;
+    if (c * 8 < rows * K) {
+      int r = (c * 8) / K, k = c * 8 - r * K;     // one division per chunk, then walk
+      if (K % 8 == 0) {                            // chunk inside one row: one 16-B LDS store
+        if constexpr (PRO >= 0) {
+          Pack8 p;
+          p.u = rb[i];
+          float psv[8], phv[8];
+          pro(psv, phv);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) p.e[j] = f2bf(act_fwd(bf2f(p.e[j]) * psv[j] + phv[j], PRO));
+          *(uint4*)(As + r * LDA + k) = p.u;
+        } else {
+          *(uint4*)(As + r * LDA + k) = rb[i];
+        }
+      } else {
+        Pack8 p;
+        p.u = rb[i];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          As[r * LDA + k] = p.e[j];
+          if (++k == K) { k = 0; ++r; }
+        }
+      }
+    }
+  }
+}
+
+// Os <- bf16(act(As W^T + bv)), Os aliasing As: each wave its 64 rows, the k-steps in order, a
+// barrier between the last MFMA read of As and the first staging store and one after the staging
+template <int KP, int NP, int ACT>
+__device__ __forceinline__ void pw_mfma_stage(bf16* As, const bf16x8 (&fb)[KP / 32][NP / 16],
+                                              const float (&bv)[NP / 16]) {
+  constexpr int LDA = KP + 8, LDO = NP + 8, KS = KP / 32, NT = NP / 16;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lr = lane & 15, lg = lane >> 4;
+  bf16* Os = As;
+  const bf16* arow = As + (wave * 64 + lr) * LDA + lg * 8;   // this lane's A-fragment row of m-tile 0
+  f32x4 acc[4][NT];
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+      const bf16x8 fa = *(const bf16x8*)(arow + mt * 16 * LDA + ks * 32);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt)
+        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[ks][nt], acc[mt][nt], 0, 0, 0);
+    }
+  __syncthreads();                               // all MFMA reads of As done before Os overwrites it
+#pragma unroll
+  for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        Os[(wave * 64 + mt * 16 + lg * 4 + r) * LDO + nt * 16 + lr] = f2bf(act_fwd(acc[mt][nt][r] + bv[nt], ACT));
+  __syncthreads();
+}
 
 // Y = act(X W^T + b).  KP / NP: K, N padded to 32 / 64.  Dynamic LDS: the A tile
 // [256][KP+8] and the output staging [256][NP+8] share one region (bf16).
@@ -49,44 +179,16 @@ __global__ __launch_bounds__(PW_NTHR, 2) void pw_fwd_kernel(const bf16* __restri
                                                            const long long* __restrict__ labels = nullptr,
                                                            float* __restrict__ xpart = nullptr, float xscale = 0.f,
                                                            float smoothing = 0.f) {
-  constexpr int LDA = KP + 8, LDO = NP + 8;
-  constexpr int KS = KP / 32, NT = NP / 16;
-  constexpr int CH = KP / 8;                     // 16-B chunks per thread of a 256 x KP tile
+  constexpr int LDO = NP + 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char pw_dsm[];
   bf16* As = reinterpret_cast<bf16*>(pw_dsm);
   bf16* Os = As;                                 // aliased: staged only after the MFMAs have read As
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, lg = lane >> 4;
 
-  auto zero_pad = [&]() {                       // K padding of the A tile (the scatter never writes it)
-    for (int i = tid; i < PW_BM * (LDA - K); i += PW_NTHR) As[(i / (LDA - K)) * LDA + K + i % (LDA - K)] = f2bf(0.f);
-  };
-  // weights -> B fragments (k rows beyond K and n cols beyond N are zero)
-  bf16x8 fb[KS][NT];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const int n = nt * 16 + lr;
-      Pack8 p;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = ks * 32 + lg * 8 + j;
-        p.e[j] = (n < N && k < K) ? w[(long long)n * K + k] : f2bf(0.f);
-      }
-      fb[ks][nt] = __builtin_bit_cast(bf16x8, p.u);
-    }
-  float bv[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int n = nt * 16 + lr;
-    bv[nt] = (HAS_BIAS && n < N) ? bias[n] : 0.f;
-  }
-
-  // optional input prologue x <- act(x * psc[k] + psh[k]) (a BatchNorm + activation whose
-  // normalised output is never written): with K % 8 == 0 and 2048 % K == 0 (host check)
-  // every chunk this thread loads starts at channel (8 tid) mod K, so 8 scale/shift pairs
-  // in registers cover all of them
+  bf16x8 fb[KP / 32][NP / 16];                   // weights live in registers for the whole kernel
+  float bv[NP / 16];
+  pw_weights<KP / 32, NP / 16, HAS_BIAS>(w, bias, K, N, fb, bv);
+  // the input prologue's 8 scale / shift pairs of this thread (see pw_scatter), in registers
   constexpr int NPV = PRO >= 0 ? 8 : 1;
   float psv[NPV], phv[NPV];
   if constexpr (PRO >= 0) {
@@ -110,74 +212,20 @@ __global__ __launch_bounds__(PW_NTHR, 2) void pw_fwd_kernel(const bf16* __restri
   }
   const int ntiles = pw_tiles(M);
   float xl = 0.f, xc = 0.f;                      // XENT: this thread's loss / top-1 hit sums
-  uint4 rb[CH];
-  auto load = [&](int t) {                       // tile t: 256*K contiguous bf16 (16-B aligned: 512*K*t)
-    const long long e0 = (long long)t * PW_BM * K;
-    const long long nel = (M - (long long)t * PW_BM < PW_BM ? M - (long long)t * PW_BM : PW_BM) * K;
+  auto pro = [&](float (&s)[8], float (&h)[8]) {
 #pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int c = i * PW_NTHR + tid;
-      // M % 8 == 0 (host check): every tile is a whole number of 16-B chunks
-      rb[i] = *(const uint4*)(x + e0 + (c * 8 < nel ? c * 8 : 0));
-    }
+    for (int j = 0; j < NPV; ++j) { s[j] = psv[j]; h[j] = phv[j]; }
   };
+  uint4 rb[KP / 8];
   int t = blockIdx.x;
-  if (t < ntiles) load(t);
+  if (t < ntiles) pw_load(x, M, K, t, rb);
   for (; t < ntiles; t += gridDim.x) {
-    const int rows = (int)(M - (long long)t * PW_BM < PW_BM ? M - (long long)t * PW_BM : PW_BM);
+    const int rows = pw_rows(M, t);
     __syncthreads();                             // previous tile's Os readers are done
-    zero_pad();                                  // Os staging overwrote the padding
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {            // scatter flat chunk -> padded rows
-      const int c = i * PW_NTHR + tid;
-      if (c * 8 < rows * K) {
-        int r = (c * 8) / K, k = c * 8 - r * K;   // one division per chunk, then walk
-        if (K % 8 == 0) {                          // chunk inside one row: one 16-B LDS store
-          if constexpr (PRO >= 0) {
-            Pack8 p;
-            p.u = rb[i];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) p.e[j] = f2bf(act_fwd(bf2f(p.e[j]) * psv[j] + phv[j], PRO));
-            *(uint4*)(As + r * LDA + k) = p.u;
-          } else {
-            *(uint4*)(As + r * LDA + k) = rb[i];
-          }
-        } else {
-          Pack8 p;
-          p.u = rb[i];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            As[r * LDA + k] = p.e[j];
-            if (++k == K) { k = 0; ++r; }
-          }
-        }
-      }
-    }
+    pw_scatter<KP, PRO>(As, rb, rows, K, pro);
     __syncthreads();
-    if (t + gridDim.x < ntiles) load(t + gridDim.x);   // next tile in flight during the MFMAs
-    f32x4 acc[4][NT];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const bf16x8 fa = *(const bf16x8*)(As + (wave * 64 + mt * 16 + lr) * LDA + ks * 32 + lg * 8);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[ks][nt], acc[mt][nt], 0, 0, 0);
-      }
-    __syncthreads();                             // all MFMA reads of As done before Os overwrites it
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          Os[(wave * 64 + mt * 16 + lg * 4 + r) * LDO + nt * 16 + lr] = f2bf(act_fwd(acc[mt][nt][r] + bv[nt], ACT));
-    __syncthreads();
+    if (t + gridDim.x < ntiles) pw_load(x, M, K, t + gridDim.x, rb);   // next tile in flight during the MFMAs
+    pw_mfma_stage<KP, NP, ACT>(As, fb, bv);
     if constexpr (XENT) {
       // one row per thread, from the stored bf16 logits (the values the unfused loss would read)
       if (tid < rows) {
@@ -281,14 +329,15 @@ __global__ __launch_bounds__(PW_NTHR, 2) void pw_fwd_kernel(const bf16* __restri
 }
 
 // Classifier head for inference: labels[row] = argmax_n (X W^T + b)[row][n] (+ optionally the top-1
-// softmax probability), the per-voxel output of the segmentation model.  pw_fwd_kernel's streaming
-// structure (persistent workgroups over 256-row tiles, the next tile's 16-B loads in flight during
-// the MFMAs, weights as register B fragments, the BN + act input prologue on the chunk before the
-// LDS scatter, the same k-step order) up to the bf16 logit tile staged in LDS -- bit for bit what
-// pw_fwd_kernel<.., ACT_NONE, ..> would have stored -- then every thread takes one row: a strict
-// `>` scan from class 0 (the lowest index wins ties) and, when asked, 1 / sum exp(v - max) in fp32
-// over the bf16 logits.  The logits never reach HBM: a tile writes 256 label bytes (+ 512
-// confidence bytes) instead of 256 * N * 2.  NP: N padded to 16 / 32 / 64.
+// softmax probability), the per-voxel output of the segmentation model.  The kernel shares its
+// front half with pw_fwd_kernel: the same pw_weights / pw_load / pw_scatter / pw_mfma_stage calls in
+// the same persistent tile loop produce the bf16 logit tile staged in LDS, so the tile is what
+// pw_fwd_kernel<.., ACT_NONE, ..> stores and the labels are the arg-max of pw_fwd's logits by
+// construction (only where the prologue's scale / shift pairs are kept differs, see below).  Then
+// every thread takes one row: a strict `>` scan from class 0 (the lowest index wins ties) and,
+// when asked, 1 / sum exp(v - max) in fp32 over the bf16 logits.  The logits never reach HBM: a
+// tile writes 256 label bytes (+ 512 confidence bytes) instead of 256 * N * 2.  NP: N padded to
+// 16 / 32 / 64.
 //
 // CM (the scorer): the row's arg-max is not (only) stored but counted against truth[row] in a
 // per-workgroup confusion histogram hist[N*N + 1] (uint32, in the dynamic LDS behind the tile):
@@ -302,42 +351,18 @@ __global__ __launch_bounds__(PW_NTHR, (KP <= 32 && NP <= 32) ? 4 : 2) void pw_ar
     uint8_t* __restrict__ labels, bf16* __restrict__ conf, long long M, int K, int N,
     const float* __restrict__ psc, const float* __restrict__ psh, const uint8_t* __restrict__ truth = nullptr,
     uint32_t* __restrict__ part = nullptr, int ignore = -1) {
-  constexpr int LDA = KP + 8, LDO = NP + 8;
-  constexpr int KS = KP / 32, NT = NP / 16;
-  constexpr int CH = KP / 8;                     // 16-B chunks per thread of a 256 x KP tile
+  constexpr int LDO = NP + 8;
   constexpr int UR = NP >= 64 ? 2 : NP / 8;      // row scan: 16-B logit chunks in flight (VGPR budget)
   extern __shared__ __attribute__((aligned(16))) unsigned char pw_dsm[];
   bf16* As = reinterpret_cast<bf16*>(pw_dsm);
   bf16* Os = As;                                 // aliased: staged only after the MFMAs have read As
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, lg = lane >> 4;
+  const int tid = threadIdx.x;
 
-  auto zero_pad = [&]() {                       // K padding of the A tile (the scatter never writes it)
-    for (int i = tid; i < PW_BM * (LDA - K); i += PW_NTHR) As[(i / (LDA - K)) * LDA + K + i % (LDA - K)] = f2bf(0.f);
-  };
-  bf16x8 fb[KS][NT];                             // weights -> B fragments (zero beyond K / N)
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      const int n = nt * 16 + lr;
-      Pack8 p;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = ks * 32 + lg * 8 + j;
-        p.e[j] = (n < N && k < K) ? w[(long long)n * K + k] : f2bf(0.f);
-      }
-      fb[ks][nt] = __builtin_bit_cast(bf16x8, p.u);
-    }
-  float bv[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int n = nt * 16 + lr;
-    bv[nt] = (HAS_BIAS && n < N) ? bias[n] : 0.f;
-  }
-  // input prologue parameters: every chunk of this thread starts at channel (8 tid) mod K (host
-  // check K % 8 == 0, 2048 % K == 0, as pw_fwd_kernel), but the 8 scale / shift pairs stay in LDS
-  // and are read per tile -- 16 fewer registers live across the MFMAs and the row scan
+  bf16x8 fb[KP / 32][NP / 16];
+  float bv[NP / 16];
+  pw_weights<KP / 32, NP / 16, HAS_BIAS>(w, bias, K, N, fb, bv);
+  // the input prologue's 8 scale / shift pairs of this thread (see pw_scatter) stay in LDS and are
+  // read per chunk -- unlike pw_fwd_kernel's, 16 fewer registers live across the MFMAs and the row scan
   __shared__ __attribute__((aligned(16))) float pss[PRO >= 0 ? 2 * KP : 4];
   const int pk0 = PRO >= 0 ? (tid * 8) % K : 0;
   if constexpr (PRO >= 0) {
@@ -346,83 +371,27 @@ __global__ __launch_bounds__(PW_NTHR, (KP <= 32 && NP <= 32) ? 4 : 2) void pw_ar
       pss[KP + tid] = psh[tid];
     }
   }
+  auto pro = [&](float (&s)[8], float (&h)[8]) {
+    const float4 s0 = *(const float4*)(pss + pk0), s1 = *(const float4*)(pss + pk0 + 4);
+    const float4 h0 = *(const float4*)(pss + KP + pk0), h1 = *(const float4*)(pss + KP + pk0 + 4);
+    s[0] = s0.x, s[1] = s0.y, s[2] = s0.z, s[3] = s0.w, s[4] = s1.x, s[5] = s1.y, s[6] = s1.z, s[7] = s1.w;
+    h[0] = h0.x, h[1] = h0.y, h[2] = h0.z, h[3] = h0.w, h[4] = h1.x, h[5] = h1.y, h[6] = h1.z, h[7] = h1.w;
+  };
   // CM: the workgroup's histogram, zeroed once (the tile loop's barriers order it before the adds)
-  uint32_t* hist = reinterpret_cast<uint32_t*>(pw_dsm + (size_t)PW_BM * ((KP > NP ? KP : NP) + 8) * 2);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(pw_dsm + pw_tile_lds(KP, NP));
   if constexpr (CM)
     for (int i = tid; i <= N * N; i += PW_NTHR) hist[i] = 0u;
   const int ntiles = pw_tiles(M);
-  uint4 rb[CH];
-  auto load = [&](int t) {                       // tile t: 256*K contiguous bf16 (16-B aligned: 512*K*t)
-    const long long e0 = (long long)t * PW_BM * K;
-    const long long nel = (M - (long long)t * PW_BM < PW_BM ? M - (long long)t * PW_BM : PW_BM) * K;
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const int c = i * PW_NTHR + tid;
-      // M % 8 == 0 (host check): every tile is a whole number of 16-B chunks
-      rb[i] = *(const uint4*)(x + e0 + (c * 8 < nel ? c * 8 : 0));
-    }
-  };
+  uint4 rb[KP / 8];
   int t = blockIdx.x;
-  if (t < ntiles) load(t);
+  if (t < ntiles) pw_load(x, M, K, t, rb);
   for (; t < ntiles; t += gridDim.x) {
-    const int rows = (int)(M - (long long)t * PW_BM < PW_BM ? M - (long long)t * PW_BM : PW_BM);
+    const int rows = pw_rows(M, t);
     __syncthreads();                             // previous tile's Os readers are done
-    zero_pad();                                  // Os staging overwrote the padding
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {            // scatter flat chunk -> padded rows
-      const int c = i * PW_NTHR + tid;
-      if (c * 8 < rows * K) {
-        int r = (c * 8) / K, k = c * 8 - r * K;
-        if (K % 8 == 0) {                          // chunk inside one row: one 16-B LDS store
-          if constexpr (PRO >= 0) {
-            Pack8 p;
-            p.u = rb[i];
-            const float4 s0 = *(const float4*)(pss + pk0), s1 = *(const float4*)(pss + pk0 + 4);
-            const float4 h0 = *(const float4*)(pss + KP + pk0), h1 = *(const float4*)(pss + KP + pk0 + 4);
-            const float psv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-            const float phv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-#pragma unroll
-            for (int j = 0; j < 8; ++j) p.e[j] = f2bf(act_fwd(bf2f(p.e[j]) * psv[j] + phv[j], PRO));
-            *(uint4*)(As + r * LDA + k) = p.u;
-          } else {
-            *(uint4*)(As + r * LDA + k) = rb[i];
-          }
-        } else {
-          Pack8 p;
-          p.u = rb[i];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            As[r * LDA + k] = p.e[j];
-            if (++k == K) { k = 0; ++r; }
-          }
-        }
-      }
-    }
+    pw_scatter<KP, PRO>(As, rb, rows, K, pro);
     __syncthreads();
-    if (t + gridDim.x < ntiles) load(t + gridDim.x);   // next tile in flight during the MFMAs
-    f32x4 acc[4][NT];
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const bf16x8 fa = *(const bf16x8*)(As + (wave * 64 + mt * 16 + lr) * LDA + ks * 32 + lg * 8);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[ks][nt], acc[mt][nt], 0, 0, 0);
-      }
-    __syncthreads();                             // all MFMA reads of As done before Os overwrites it
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          Os[(wave * 64 + mt * 16 + lg * 4 + r) * LDO + nt * 16 + lr] = f2bf(acc[mt][nt][r] + bv[nt]);
-    __syncthreads();
+    if (t + gridDim.x < ntiles) pw_load(x, M, K, t + gridDim.x, rb);   // next tile in flight during the MFMAs
+    pw_mfma_stage<KP, NP, ACT_NONE>(As, fb, bv);
     // one row per thread, 16-B LDS reads of the staged bf16 logits: a running scan, no per-class
     // array (columns N .. NP are padding and never compete)
     if (tid < rows) {
@@ -518,15 +487,6 @@ __global__ __launch_bounds__(PW_NTHR, 2) void pw_wgrad_kernel(const bf16* __rest
   const int ntiles = pw_tiles(M);
   constexpr int CY = NP / 8, CX = KP / 8;        // 16-B chunks per thread of the dy / x tiles
   uint4 ry[CY], rx[CX];
-  auto load = [&](const bf16* src, int C, int t, uint4* rb, int nch) {
-    const long long e0 = (long long)t * PW_BM * C;
-    const long long nel = (M - (long long)t * PW_BM < PW_BM ? M - (long long)t * PW_BM : PW_BM) * C;
-#pragma unroll
-    for (int i = 0; i < nch; ++i) {
-      const int c = i * PW_NTHR + tid;
-      rb[i] = *(const uint4*)(src + e0 + (c * 8 < nel ? c * 8 : 0));
-    }
-  };
   // optional prologue on x (as pw_fwd_kernel): x <- act(x * psc[k] + psh[k])
   auto scatter_t = [&](bf16* dst, const uint4* rb, int C, int rows, int nch) {
 #pragma unroll
@@ -545,9 +505,9 @@ __global__ __launch_bounds__(PW_NTHR, 2) void pw_wgrad_kernel(const bf16* __rest
     }
   };
   int t = blockIdx.x;
-  if (t < ntiles) { load(dy, N, t, ry, CY); load(x, K, t, rx, CX); }
+  if (t < ntiles) { pw_load(dy, M, N, t, ry); pw_load(x, M, K, t, rx); }
   for (; t < ntiles; t += gridDim.x) {
-    const int rows = (int)(M - (long long)t * PW_BM < PW_BM ? M - (long long)t * PW_BM : PW_BM);
+    const int rows = pw_rows(M, t);
     __syncthreads();
     scatter_t(Yt, ry, N, rows, CY);
     scatter_t(Xt, rx, K, rows, CX);
@@ -573,7 +533,7 @@ __global__ __launch_bounds__(PW_NTHR, 2) void pw_wgrad_kernel(const bf16* __rest
       }
       __syncthreads();
     }
-    if (t + gridDim.x < ntiles) { load(dy, N, t + gridDim.x, ry, CY); load(x, K, t + gridDim.x, rx, CX); }
+    if (t + gridDim.x < ntiles) { pw_load(dy, M, N, t + gridDim.x, ry); pw_load(x, M, K, t + gridDim.x, rx); }
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       const int r0 = wave * 64 + kk * 32 + lg * 8;
@@ -628,6 +588,31 @@ static bool pw_pro_ok(const float* psc, const float* psh, int K) {
   return !psc || (psh && K % 8 == 0 && 2048 % K == 0);
 }
 
+// The runtime (K, N, bias or not, prologue or not and its activation) as the compile-time tags
+// (KP, NP, HAS_BIAS, PRO) of a kernel instance: f(KP, NP, HB, PRO) gets std::integral_constants and
+// returns the entry point's status.  NP16: N <= 16 selects NP = 16 (the arg-max instances), else 32.
+template <int V>
+using pw_int = std::integral_constant<int, V>;
+
+template <bool NP16 = false, class F>
+static int pw_dispatch(int K, int N, bool hb, bool pro, int pact, F f) {
+  auto with_pro = [&](auto KP, auto NP, auto HB) {
+    if (!pro) return f(KP, NP, HB, pw_int<-1>{});
+    if (pact == ACT_RELU) return f(KP, NP, HB, pw_int<ACT_RELU>{});
+    return f(KP, NP, HB, pw_int<ACT_NONE>{});
+  };
+  auto with_hb = [&](auto KP, auto NP) {
+    return hb ? with_pro(KP, NP, std::true_type{}) : with_pro(KP, NP, std::false_type{});
+  };
+  auto with_np = [&](auto KP) {
+    if constexpr (NP16) {
+      if (N <= 16) return with_hb(KP, pw_int<16>{});
+    }
+    return N <= 32 ? with_hb(KP, pw_int<32>{}) : with_hb(KP, pw_int<64>{});
+  };
+  return K <= 32 ? with_np(pw_int<32>{}) : with_np(pw_int<64>{});
+}
+
 // grid of the BWS (dgrad + BN-backward moments) launch = rows of its spart slab: 3 workgroups per
 // CU (165 VGPRs: occupancy 3, so a 4-per-CU persistent grid would leave a serial tail)
 extern "C" int fn_pw_fwd_blocks(long long M, int K, int N) {
@@ -640,66 +625,49 @@ extern "C" int fn_pw_fwd(const void* x, const void* w, const float* bias, void* 
                          const float* ssc, const float* ssh, float* spart, int sact) {
   if (K < 1 || K > 64 || N < 1 || N > 64 || M < 8 || M % 8) return -2;
   if (!pw_pro_ok(psc, psh, K)) return -2;
-  // ~110-200 VGPRs and <= 37 KB LDS: 4 workgroups per CU for the 32-channel variants
-  const dim3 grid((unsigned)pw_grid(M, (K <= 32 && N <= 32) ? 4 : 2));
-  if (sy) {                                      // dgrad + BN-backward moments (see BWS)
+  if (sy) {                                      // dgrad + BN-backward moments (see BWS): 32 x 32 only
     if (psc || bias || act != ACT_NONE || !ssc || !ssh || !spart || N % 8 || 2048 % N ||
         (sact != ACT_NONE && sact != ACT_RELU) || K > 32 || N > 32)
       return -2;
-#define PWS(SA)                                                                                              \
-  hipLaunchKernelGGL((pw_fwd_kernel<32, 32, ACT_NONE, false, -1, SA>), dim3((unsigned)fn_pw_fwd_blocks(M, K, N)),  \
-                     dim3(PW_NTHR),                                                                            \
-                     (size_t)PW_BM * (32 + 8) * 2, st, (const bf16*)x, (const bf16*)w, nullptr, (bf16*)y, M, K, N, \
-                     nullptr, nullptr, (const bf16*)sy, ssc, ssh, spart)
-    if (sact == ACT_RELU) PWS(ACT_RELU); else PWS(ACT_NONE);
-#undef PWS
+    auto bws = [&](auto SA) {
+      hipLaunchKernelGGL((pw_fwd_kernel<32, 32, ACT_NONE, false, -1, decltype(SA)::value>),
+                         dim3((unsigned)fn_pw_fwd_blocks(M, K, N)), dim3(PW_NTHR), pw_tile_lds(32, 32), st,
+                         (const bf16*)x, (const bf16*)w, nullptr, (bf16*)y, M, K, N, nullptr, nullptr, (const bf16*)sy,
+                         ssc, ssh, spart);
+    };
+    if (sact == ACT_RELU) bws(pw_int<ACT_RELU>{}); else bws(pw_int<ACT_NONE>{});
     FN_CHECK_LAUNCH();
     return 0;
   }
-  const bool hb = bias != nullptr;
-  // (the 64-channel prologue instances need > 64 KB of LDS only for KP = NP = 64: not emitted)
-#define PWF(KP, NP, A, HB)                                                                                   \
-  do {                                                                                                         \
-    const size_t lds = (size_t)PW_BM * ((KP > NP ? KP : NP) + 8) * 2;                                        \
-    if (lds > 64 * 1024 &&                                                                                     \
-        hipFuncSetAttribute((const void*)pw_fwd_kernel<KP, NP, A, HB>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            (int)lds) != hipSuccess)                                                           \
-      return -4;                                                                                               \
-    hipLaunchKernelGGL((pw_fwd_kernel<KP, NP, A, HB>), grid, dim3(PW_NTHR), lds, st, (const bf16*)x,          \
-                       (const bf16*)w, bias, (bf16*)y, M, K, N, nullptr, nullptr);                             \
-  } while (0)
-  // prologue instances (the BN + act of the producing layer): identity output, bias or not,
-  // K <= 32 or 64, N <= 32 or 64
-#define PWP(KP, NP, HB, PA)                                                                                  \
-  hipLaunchKernelGGL((pw_fwd_kernel<KP, NP, ACT_NONE, HB, PA>), grid, dim3(PW_NTHR),                           \
-                     (size_t)PW_BM * ((KP > NP ? KP : NP) + 8) * 2, st, (const bf16*)x, (const bf16*)w, bias,    \
-                     (bf16*)y, M, K, N, psc, psh)
   if (psc) {
     if (act != ACT_NONE || (pact != ACT_NONE && pact != ACT_RELU)) return -2;
-#define PWP2(KP, NP)                                                                                         \
-    do {                                                                                                     \
-      if (pact == ACT_RELU) { if (hb) PWP(KP, NP, true, ACT_RELU); else PWP(KP, NP, false, ACT_RELU); }      \
-      else { if (hb) PWP(KP, NP, true, ACT_NONE); else PWP(KP, NP, false, ACT_NONE); }                       \
-    } while (0)
-    if (K <= 32) { if (N <= 32) PWP2(32, 32); else PWP2(32, 64); }
-    else { if (N <= 32) PWP2(64, 32); else PWP2(64, 64); }
-#undef PWP2
-#undef PWP
-    FN_CHECK_LAUNCH();
-    return 0;
+  } else if ((act == ACT_TANH || act == ACT_SIGMOID) && !bias) {
+    return -5;
   }
-#define PWA(KP, NP)                                                          \
-  do {                                                                       \
-    if (act == ACT_RELU) { if (hb) PWF(KP, NP, ACT_RELU, true); else PWF(KP, NP, ACT_RELU, false); } \
-    else if (act == ACT_NONE) { if (hb) PWF(KP, NP, ACT_NONE, true); else PWF(KP, NP, ACT_NONE, false); } \
-    else if (act == ACT_TANH) PWF(KP, NP, ACT_TANH, true);                  \
-    else PWF(KP, NP, ACT_SIGMOID, true);                                     \
-  } while (0)
-  if ((act == ACT_TANH || act == ACT_SIGMOID) && !hb) return -5;
-  if (K <= 32) { if (N <= 32) PWA(32, 32); else PWA(32, 64); }
-  else { if (N <= 32) PWA(64, 32); else PWA(64, 64); }
-#undef PWA
-#undef PWF
+  // ~110-200 VGPRs and <= 37 KB LDS: 4 workgroups per CU for the 32-channel variants
+  const dim3 grid((unsigned)pw_grid(M, (K <= 32 && N <= 32) ? 4 : 2));
+  // instances: the prologue (the BN + act of the producing layer) has the identity output only;
+  // tanh and sigmoid exist with a bias only
+  const int rc = pw_dispatch(K, N, bias != nullptr, psc != nullptr, pact, [&](auto KP, auto NP, auto HB, auto PRO) {
+    constexpr int kp = decltype(KP)::value, np = decltype(NP)::value, pro = decltype(PRO)::value;
+    constexpr bool hb = decltype(HB)::value;
+    auto go = [&](auto ACT) {
+      constexpr size_t lds = pw_tile_lds(kp, np);
+      if (lds > 64 * 1024 &&
+          hipFuncSetAttribute((const void*)pw_fwd_kernel<kp, np, decltype(ACT)::value, hb, pro>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -4;
+      hipLaunchKernelGGL((pw_fwd_kernel<kp, np, decltype(ACT)::value, hb, pro>), grid, dim3(PW_NTHR), lds, st,
+                         (const bf16*)x, (const bf16*)w, bias, (bf16*)y, M, K, N, psc, psh);
+      return 0;
+    };
+    if constexpr (pro >= 0) return go(pw_int<ACT_NONE>{});
+    else if (act == ACT_RELU) return go(pw_int<ACT_RELU>{});
+    else if (act == ACT_NONE) return go(pw_int<ACT_NONE>{});
+    else if constexpr (hb) return act == ACT_TANH ? go(pw_int<ACT_TANH>{}) : go(pw_int<ACT_SIGMOID>{});
+    else return -5;
+  });
+  if (rc) return rc;
   FN_CHECK_LAUNCH();
   return 0;
 }
@@ -716,16 +684,13 @@ extern "C" int fn_pw_fwd_xent(const void* x, const void* w, const float* bias, v
   if (K < 1 || K > 32 || N < 2 || N > 32 || M < 8 || M % 8 || !labels || !xpart) return -2;
   if (!pw_pro_ok(psc, psh, K) || (psc && pact != ACT_NONE && pact != ACT_RELU)) return -2;
   const dim3 grid((unsigned)fn_pw_xent_blocks(M));
-  const size_t lds = (size_t)PW_BM * (32 + 8) * 2;
-  const bool hb = bias != nullptr;
-#define PWX(HB, PA)                                                                                          \
-  hipLaunchKernelGGL((pw_fwd_kernel<32, 32, ACT_NONE, HB, PA, -1, true>), grid, dim3(PW_NTHR), lds, st,       \
-                     (const bf16*)x, (const bf16*)w, bias, (bf16*)dlog, M, K, N, psc, psh, nullptr, nullptr,     \
-                     nullptr, nullptr, labels, xpart, xscale, smoothing)
-  if (!psc) { if (hb) PWX(true, -1); else PWX(false, -1); }
-  else if (pact == ACT_RELU) { if (hb) PWX(true, ACT_RELU); else PWX(false, ACT_RELU); }
-  else { if (hb) PWX(true, ACT_NONE); else PWX(false, ACT_NONE); }
-#undef PWX
+  pw_dispatch(K, N, bias != nullptr, psc != nullptr, pact, [&](auto KP, auto NP, auto HB, auto PRO) {
+    if constexpr (decltype(KP)::value == 32 && decltype(NP)::value == 32)   // (K, N <= 32 above)
+      hipLaunchKernelGGL((pw_fwd_kernel<32, 32, ACT_NONE, decltype(HB)::value, decltype(PRO)::value, -1, true>), grid,
+                         dim3(PW_NTHR), pw_tile_lds(32, 32), st, (const bf16*)x, (const bf16*)w, bias, (bf16*)dlog, M, K,
+                         N, psc, psh, nullptr, nullptr, nullptr, nullptr, labels, xpart, xscale, smoothing);
+    return 0;
+  });
   FN_CHECK_LAUNCH();
   return 0;
 }
@@ -740,28 +705,20 @@ extern "C" int fn_pw_wgrad(const void* dy, const void* x, float* dw, long long M
   if (K < 1 || K > 64 || N < 1 || N > 64 || M < 8 || M % 8) return -2;
   if (!pw_pro_ok(psc, psh, K)) return -2;
   if (!part) return -6;
-  const dim3 grid((unsigned)fn_pw_wgrad_blocks(M, K, N));
-#define PWW(KP, NP)                                                                                          \
-  do {                                                                                                     \
-    const size_t lds = (size_t)(KP + NP) * (PW_BM + 8) * 2;                                                \
-    if (lds > 64 * 1024 &&                                                                                 \
-        hipFuncSetAttribute((const void*)pw_wgrad_kernel<KP, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            (int)lds) != hipSuccess)                                                       \
-      return -4;                                                                                           \
-    if (!psc)                                                                                              \
-      hipLaunchKernelGGL((pw_wgrad_kernel<KP, NP>), grid, dim3(PW_NTHR), lds, st, (const bf16*)dy,        \
-                         (const bf16*)x, part, M, K, N, nullptr, nullptr);                                 \
-    else if (pact == ACT_RELU)                                                                             \
-      hipLaunchKernelGGL((pw_wgrad_kernel<KP, NP, ACT_RELU>), grid, dim3(PW_NTHR), lds, st, (const bf16*)dy, \
-                         (const bf16*)x, part, M, K, N, psc, psh);                                         \
-    else                                                                                                   \
-      hipLaunchKernelGGL((pw_wgrad_kernel<KP, NP, ACT_NONE>), grid, dim3(PW_NTHR), lds, st, (const bf16*)dy, \
-                         (const bf16*)x, part, M, K, N, psc, psh);                                         \
-  } while (0)
   if (psc && pact != ACT_NONE && pact != ACT_RELU) return -2;
-  if (K <= 32) { if (N <= 32) PWW(32, 32); else PWW(32, 64); }
-  else { if (N <= 32) PWW(64, 32); else PWW(64, 64); }
-#undef PWW
+  const dim3 grid((unsigned)fn_pw_wgrad_blocks(M, K, N));
+  const int rc = pw_dispatch(K, N, false, psc != nullptr, pact, [&](auto KP, auto NP, auto, auto PRO) {
+    constexpr int kp = decltype(KP)::value, np = decltype(NP)::value;
+    constexpr size_t lds = pw_wgrad_lds(kp, np);
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)pw_wgrad_kernel<kp, np>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
+      return -4;
+    hipLaunchKernelGGL((pw_wgrad_kernel<kp, np, decltype(PRO)::value>), grid, dim3(PW_NTHR), lds, st, (const bf16*)dy,
+                       (const bf16*)x, part, M, K, N, psc, psh);
+    return 0;
+  });
+  if (rc) return rc;
   FN_CHECK_LAUNCH();
   return fn_part_reduce(part, dw, (long long)N * K, (int)grid.x, 1, st);
 }
@@ -779,21 +736,13 @@ extern "C" int fn_pw_argmax(const void* x, const void* w, const float* bias, voi
   if (K < 1 || K > 64 || N < 1 || N > 64 || M < 8 || M % 8 || !labels) return -2;
   if (!pw_pro_ok(psc, psh, K) || (psc && pact != ACT_NONE && pact != ACT_RELU)) return -2;
   const dim3 grid((unsigned)fn_pw_argmax_blocks(M, K, N));
-  const bool hb = bias != nullptr;
-#define PWM(KP, NP, HB, PA)                                                                                  \
-  hipLaunchKernelGGL((pw_argmax_kernel<KP, NP, HB, PA>), grid, dim3(PW_NTHR),                                  \
-                     (size_t)PW_BM * ((KP > NP ? KP : NP) + 8) * 2, st, (const bf16*)x, (const bf16*)w, bias,    \
-                     (uint8_t*)labels, (bf16*)conf, M, K, N, psc, psh)
-#define PWM2(KP, NP)                                                                                         \
-  do {                                                                                                       \
-    if (!psc) { if (hb) PWM(KP, NP, true, -1); else PWM(KP, NP, false, -1); }                                \
-    else if (pact == ACT_RELU) { if (hb) PWM(KP, NP, true, ACT_RELU); else PWM(KP, NP, false, ACT_RELU); }   \
-    else { if (hb) PWM(KP, NP, true, ACT_NONE); else PWM(KP, NP, false, ACT_NONE); }                         \
-  } while (0)
-  if (K <= 32) { if (N <= 16) PWM2(32, 16); else if (N <= 32) PWM2(32, 32); else PWM2(32, 64); }
-  else { if (N <= 16) PWM2(64, 16); else if (N <= 32) PWM2(64, 32); else PWM2(64, 64); }
-#undef PWM2
-#undef PWM
+  pw_dispatch<true>(K, N, bias != nullptr, psc != nullptr, pact, [&](auto KP, auto NP, auto HB, auto PRO) {
+    constexpr int kp = decltype(KP)::value, np = decltype(NP)::value;
+    hipLaunchKernelGGL((pw_argmax_kernel<kp, np, decltype(HB)::value, decltype(PRO)::value>), grid, dim3(PW_NTHR),
+                       pw_tile_lds(kp, np), st, (const bf16*)x, (const bf16*)w, bias, (uint8_t*)labels, (bf16*)conf, M,
+                       K, N, psc, psh);
+    return 0;
+  });
   FN_CHECK_LAUNCH();
   return 0;
 }
@@ -813,22 +762,14 @@ extern "C" int fn_pw_argmax_cm(const void* x, const void* w, const float* bias, 
   if (!pw_pro_ok(psc, psh, K) || (psc && pact != ACT_NONE && pact != ACT_RELU)) return -2;
   const int nb = fn_pw_argmax_cm_blocks(M, K, N), len = N * N + 1;
   const dim3 grid((unsigned)nb);
-  const bool hb = bias != nullptr;
-#define PWC(KP, NP, HB, PA)                                                                                  \
-  hipLaunchKernelGGL((pw_argmax_kernel<KP, NP, HB, PA, true>), grid, dim3(PW_NTHR),                            \
-                     (size_t)PW_BM * ((KP > NP ? KP : NP) + 8) * 2 + (size_t)len * 4, st, (const bf16*)x,        \
-                     (const bf16*)w, bias, (uint8_t*)labels, (bf16*)nullptr, M, K, N, psc, psh,                  \
-                     (const uint8_t*)truth, (uint32_t*)part, ignore)
-#define PWC2(KP, NP)                                                                                         \
-  do {                                                                                                       \
-    if (!psc) { if (hb) PWC(KP, NP, true, -1); else PWC(KP, NP, false, -1); }                                \
-    else if (pact == ACT_RELU) { if (hb) PWC(KP, NP, true, ACT_RELU); else PWC(KP, NP, false, ACT_RELU); }   \
-    else { if (hb) PWC(KP, NP, true, ACT_NONE); else PWC(KP, NP, false, ACT_NONE); }                         \
-  } while (0)
-  if (K <= 32) { if (N <= 16) PWC2(32, 16); else if (N <= 32) PWC2(32, 32); else PWC2(32, 64); }
-  else { if (N <= 16) PWC2(64, 16); else if (N <= 32) PWC2(64, 32); else PWC2(64, 64); }
-#undef PWC2
-#undef PWC
+  pw_dispatch<true>(K, N, bias != nullptr, psc != nullptr, pact, [&](auto KP, auto NP, auto HB, auto PRO) {
+    constexpr int kp = decltype(KP)::value, np = decltype(NP)::value;
+    hipLaunchKernelGGL((pw_argmax_kernel<kp, np, decltype(HB)::value, decltype(PRO)::value, true>), grid,
+                       dim3(PW_NTHR), pw_tile_lds(kp, np) + (size_t)len * 4, st, (const bf16*)x, (const bf16*)w, bias,
+                       (uint8_t*)labels, (bf16*)nullptr, M, K, N, psc, psh, (const uint8_t*)truth, (uint32_t*)part,
+                       ignore);
+    return 0;
+  });
   FN_CHECK_LAUNCH();
   hipLaunchKernelGGL(cm_accumulate_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, st,
                      (const uint32_t*)part, (long long*)acc, len, nb);

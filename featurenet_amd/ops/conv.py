@@ -793,6 +793,16 @@ def pointwise_ok(spec: ConvSpec, want_stats: bool = False) -> bool:
             and spec.M % 8 == 0 and spec.M >= 8)
 
 
+def _pw_operands(w2, bias, pro):
+    """Operands of the pointwise kernels as they take them: ``w2`` as contiguous bf16 and ``bias`` as
+    contiguous fp32 (None stays None), and the input prologue ``pro = (scale, shift, act)`` as its two
+    device pointers and activation code (0, 0, 0 without one) -> ``(wb, bias, psc, psh, pact)``."""
+    wb = None if w2 is None else w2.detach().to(torch.bfloat16).contiguous()
+    bias = None if bias is None else bias.detach().float().contiguous()
+    psc, psh, pact = pro if pro is not None else (None, None, 0)
+    return wb, bias, _native.ptr(psc), _native.ptr(psh), pact
+
+
 def pw_fwd(x2: torch.Tensor, w2: torch.Tensor, bias, act: int, pro=None) -> torch.Tensor:
     """[M, Kin] x [Nout, Kin]^T (+bias, act) -> bf16 [M, Nout] on the pointwise kernel.
 
@@ -803,10 +813,9 @@ def pw_fwd(x2: torch.Tensor, w2: torch.Tensor, bias, act: int, pro=None) -> torc
     if act and bias is None:
         bias = torch.zeros(N, dtype=torch.float32, device=x2.device)
     y = torch.empty(M, N, dtype=torch.bfloat16, device=x2.device)
-    wb = w2.detach().to(torch.bfloat16).contiguous()
-    psc, psh, pact = pro if pro is not None else (None, None, 0)
+    wb, bias, psc, psh, pact = _pw_operands(w2, bias, pro)
     _native.kernels().pw_fwd(x2.data_ptr(), wb.data_ptr(), _native.ptr(bias), y.data_ptr(), M, Kin, N, act,
-                             _native.stream(x2), _native.ptr(psc), _native.ptr(psh), pact)
+                             _native.stream(x2), psc, psh, pact)
     return y
 
 
@@ -837,11 +846,9 @@ def pw_argmax(x2: torch.Tensor, w2: torch.Tensor, bias, pro=None, want_conf: boo
         x2 = x2.to(torch.bfloat16).contiguous()
         labels = torch.empty(M, dtype=torch.uint8, device=x2.device)
         conf = torch.empty(M, dtype=torch.bfloat16, device=x2.device) if want_conf else None
-        wb = w2.detach().to(torch.bfloat16).contiguous()
-        bias = bias.detach().float().contiguous() if bias is not None else None
-        psc, psh, pact = pro if pro is not None else (None, None, 0)
+        wb, bias, psc, psh, pact = _pw_operands(w2, bias, pro)
         _native.kernels().pw_argmax(x2.data_ptr(), wb.data_ptr(), _native.ptr(bias), labels.data_ptr(),
-                                    _native.ptr(conf), M, Kin, N, _native.ptr(psc), _native.ptr(psh), pact,
+                                    _native.ptr(conf), M, Kin, N, psc, psh, pact,
                                     _native.stream(x2), [x2.numel(), labels.numel(), M if want_conf else 0])
         return labels, conf
     z = x2
@@ -884,14 +891,12 @@ def pw_argmax_score(x2: torch.Tensor, w2: torch.Tensor, bias, truth: torch.Tenso
     x2 = x2.to(torch.bfloat16).contiguous()
     truth = truth.reshape(-1).to(torch.uint8).contiguous()
     labels = torch.empty(M, dtype=torch.uint8, device=x2.device) if want_labels else None
-    wb = w2.detach().to(torch.bfloat16).contiguous()
-    bias = bias.detach().float().contiguous() if bias is not None else None
-    psc, psh, pact = pro if pro is not None else (None, None, 0)
+    wb, bias, psc, psh, pact = _pw_operands(w2, bias, pro)
     ignore = -1 if ignore_index is None or not 0 <= int(ignore_index) <= 255 else int(ignore_index)
     K_ = _native.kernels()
     part = torch.empty(int(K_.pw_argmax_cm_blocks(M, Kin, N)) * (N * N + 1), dtype=torch.int32, device=x2.device)
     K_.pw_argmax_cm(x2.data_ptr(), wb.data_ptr(), _native.ptr(bias), truth.data_ptr(), _native.ptr(labels),
-                    part.data_ptr(), acc.data_ptr(), M, Kin, N, ignore, _native.ptr(psc), _native.ptr(psh), pact,
+                    part.data_ptr(), acc.data_ptr(), M, Kin, N, ignore, psc, psh, pact,
                     _native.stream(x2), [x2.numel(), truth.numel(), M if want_labels else 0, part.numel(), acc.numel()])
     return acc, labels
 
@@ -905,11 +910,11 @@ def pw_wgrad(dy2: torch.Tensor, x2: torch.Tensor, pro=None, out=None) -> torch.T
         dw = out.view(N, Kin)
     else:
         dw = torch.zeros(N, Kin, dtype=torch.float32, device=x2.device)
-    psc, psh, pact = pro if pro is not None else (None, None, 0)
+    _, _, psc, psh, pact = _pw_operands(None, None, pro)
     K = _native.kernels()
     part = part_scratch(int(K.pw_wgrad_blocks(M, Kin, N)) * N * Kin, x2.device)
-    K.pw_wgrad(dy2.data_ptr(), x2.data_ptr(), dw.data_ptr(), M, Kin, N, _native.stream(x2), _native.ptr(psc),
-               _native.ptr(psh), pact, part.data_ptr(), part.numel())
+    K.pw_wgrad(dy2.data_ptr(), x2.data_ptr(), dw.data_ptr(), M, Kin, N, _native.stream(x2), psc, psh, pact,
+               part.data_ptr(), part.numel())
     return dw
 
 

@@ -11,7 +11,10 @@ and the prefetch runs):
 * oracle: against fp64 ``l = bf16(pact(x * psc + psh)) w^T + b`` the labels may differ only on rows
   whose oracle top-2 gap is below ``2^-7 max|l_row|`` (each bf16 logit is within 2^-9 relative, two
   competing logits 2^-8, times a 2x margin), and those rows stay <= 6 % of a case's rows (pooled
-  over its M values: at M = 8 one row is 12.5 %).
+  over its M values: at M = 8 one row is 12.5 %);
+* ``pw_fwd`` itself (the two kernels share the code up to the staged logit tile, so an error there
+  would cancel in the exact check): every stored logit against the same fp64 oracle, within one
+  bf16 rounding plus the fp32 accumulation error (``test_pw_fwd_against_fp64_oracle``).
 """
 import numpy as np
 import pytest
@@ -52,15 +55,20 @@ def make_inputs(M, K, N, pro, bias, seed):
     return x, w, b, p
 
 
-def oracle(x, w, b, p):
-    """fp64 logits of z = bf16(pact(x * psc + psh))."""
+def oracle_input(x, p):
+    """z = bf16(pact(x * psc + psh)) in fp64 (x itself without a prologue)."""
     z = x.double()
     if p is not None:
         z = z * p[0].double() + p[1].double()
         if p[2] == 1:
             z = torch.relu(z)
         z = z.to(torch.bfloat16).double()
-    l = z @ w.double().t()
+    return z
+
+
+def oracle(x, w, b, p):
+    """fp64 logits of z = bf16(pact(x * psc + psh))."""
+    l = oracle_input(x, p) @ w.double().t()
     return l + b.double() if b is not None else l
 
 
@@ -104,6 +112,31 @@ def test_kernel_exact_and_oracle(kn, pro, bias):
         rows, unsure = rows + M, unsure + u
     print(f"pw_argmax K={K} N={N} pro={pro} bias={bias}: oracle-undecided rows {100.0 * unsure / rows:.2f} %")
     assert unsure <= 0.06 * rows, unsure / rows
+
+
+# K = 6: the 16-B chunks straddle rows (the prologue needs K % 8 == 0, so plain input only)
+FWD_CASES = [(kn, pro) for kn in KN for pro in PRO] + [((6, 40), None)]
+PRO_IDS = {None: "plain", 0: "bn", 1: "bnrelu"}
+
+
+@pytest.mark.parametrize("bias", [True, False], ids=["bias", "nobias"])
+@pytest.mark.parametrize("case", FWD_CASES, ids=lambda c: f"k{c[0][0]}n{c[0][1]}-{PRO_IDS[c[1]]}")
+def test_pw_fwd_against_fp64_oracle(case, bias):
+    """``pw_fwd`` (the front half ``pw_argmax_kernel`` shares) against the fp64 logits l, every row and
+    element: |y - l| <= 2^-8 |l| + 2^-17 (sum_k |z_k w_k| + |b|) -- one bf16 rounding of the output
+    (half-ulp 2^-9, doubled) plus fp32 accumulation over K <= 64 terms (64 * 2^-24, doubled)."""
+    (K, N), pro = case
+    for i, M in enumerate(m_values(K, N)):
+        x, w, b, p = make_inputs(M, K, N, pro, bias, 100 + i)
+        y = C.pw_fwd(x, w, b, 0, pro=p).double()
+        l = oracle(x, w, b, p)
+        mag = oracle_input(x, p).abs() @ w.double().abs().t()
+        if b is not None:
+            mag = mag + b.double().abs()
+        excess = (y - l).abs() - (2.0 ** -8 * l.abs() + 2.0 ** -17 * mag)
+        print(f"pw_fwd K={K} N={N} pro={pro} bias={bias} M={M}: max |y - l| {float((y - l).abs().max()):.3e}, "
+              f"max (error - bound) {float(excess.max()):.3e}")
+        assert y.shape == (M, N) and float(excess.max()) <= 0.0, (M, int((excess > 0).sum()))
 
 
 @pytest.mark.parametrize("pro", PRO, ids=["plain", "bn", "bnrelu"])
