@@ -1,5 +1,6 @@
-"""Public Python API: ``train()``, ``classify()``, ``segment()``, ``evaluate()``,
-``evaluate_segmentation()``, ``load()``, ``save()``, ``build_model()`` and ``search()``.
+"""Public Python API: ``train()``, ``classify()``, ``segment()``, ``extract_features()``,
+``label_components()``, ``evaluate()``, ``evaluate_segmentation()``, ``load()``, ``save()``,
+``build_model()`` and ``search()``.
 
 Reference parity: the de-facto entry point of the reference is the
 ``TensorflowGenerator(product, epochs, dataset, ...)`` constructor
@@ -273,6 +274,81 @@ def evaluate_segmentation(model, x, y, batch_size: int = 32, device=None, packed
         raise ValueError(f"evaluate_segmentation(): {int(counts[-1])} voxels carry a label >= {C} (the model's "
                          "class count); pass ignore_index to mask unlabelled voxels")
     return SegScore.from_confusion(counts[:-1].reshape(C, C))
+
+
+@torch.no_grad()
+def extract_features(model, x, batch_size: int = 32, device=None, packed_size: int | None = None,
+                     background: int | None = 0, connectivity: int = 6, min_voxels: int = 1,
+                     return_ids: bool = False):
+    """The machining features of each part -> (one list of :class:`FeatureInstance` per sample,
+    ids int32 [N, S, S, S] or None).
+
+    ``model`` and ``x`` as for :func:`segment`.  Runs ``FeatureNet3DSeg.instances``: the per-voxel
+    labels are split into connected components of one class (``connectivity`` 6 = faces, 26 =
+    faces, edges and corners; voxels of class ``background`` -- None: no such class -- belong to
+    none) on the model's device, and only the instance table (13 integers per component) crosses
+    to the host, plus, with ``return_ids``, the volume that numbers each sample's components from
+    1 in raster order of their first voxel.  ``min_voxels`` drops smaller components from the lists
+    only: the others keep their ``id``, and ``ids`` keeps every component.
+    """
+    from .utils.seginstances import FeatureInstance
+
+    if isinstance(model, (str, Path)):
+        model, _ = load(model, device)
+    if not isinstance(model, FeatureNet3DSeg):
+        raise ValueError(f"extract_features() takes a FeatureNet3DSeg model, not {type(model).__name__} "
+                         "(see classify())")
+    if connectivity not in (6, 26):
+        raise ValueError(f"extract_features(): connectivity must be 6 or 26, not {connectivity!r}")
+    dev = next(model.parameters()).device
+    model.eval()
+    from .training.data import unpack_voxels
+
+    xt = torch.as_tensor(np.asarray(x)) if not isinstance(x, torch.Tensor) else x
+    feats, ids = [], []
+    for i in range(0, len(xt), batch_size):
+        xb = xt[i:i + batch_size].to(dev)
+        if packed_size is not None:
+            xb = unpack_voxels(xb, packed_size)
+        xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
+        table, offsets, idb = model.instances(xb, background=background, connectivity=connectivity,
+                                              want_ids=return_ids)
+        feats += FeatureInstance.from_table(table, offsets, min_voxels)
+        if return_ids:
+            ids.append(idb.cpu())
+    if not return_ids:
+        return feats, None
+    S = model.input_size
+    return feats, (torch.cat(ids).numpy() if ids else np.zeros((0, S, S, S), np.int32))
+
+
+@torch.no_grad()
+def label_components(labels, background: int | None = 0, connectivity: int = 6, device=None):
+    """Connected components of label volumes the caller already has (ground truth, say) ->
+    (ids int32 [N, D, H, W], one list of :class:`FeatureInstance` per sample).
+
+    ``labels`` is ``[N, D, H, W]`` of any integer dtype with values
+    0..255; ``background`` and ``connectivity`` as for :func:`extract_features`.  ``device``
+    defaults to the GPU when there is one (the ``ccl`` kernels), else the CPU reference path.
+    """
+    from .ops import ccl
+    from .utils.seginstances import FeatureInstance
+
+    lt = torch.as_tensor(np.asarray(labels)) if not isinstance(labels, torch.Tensor) else labels
+    if lt.is_floating_point() or lt.dtype == torch.bool:
+        raise ValueError(f"label_components(): labels must be integers, not {lt.dtype}")
+    if connectivity not in (6, 26):
+        raise ValueError(f"label_components(): connectivity must be 6 or 26, not {connectivity!r}")
+    if lt.dim() != 4:
+        raise ValueError(f"label_components(): labels must be [N, D, H, W], not {tuple(lt.shape)}")
+    if lt.dtype != torch.uint8 and lt.numel() and (int(lt.min()) < 0 or int(lt.max()) > 255):
+        raise ValueError("label_components(): label values must lie in 0..255")
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    lt = lt.to(device).to(torch.uint8).contiguous()
+    roots, flags = ccl.connected_components(lt, background, connectivity, return_flags=True)
+    ids, table, offsets = ccl.instance_table(lt, roots, want_ids=True, flags=flags)
+    return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets)
 
 
 def evaluate(model, x, y, batch_size: int = 256, packed_size: int | None = None) -> float:

@@ -15,6 +15,7 @@ train      ``TensorflowGenerator(...)`` one architecture (template / product /
 classify   load a checkpoint and predict (npy / binvox folder)
 segment    per-voxel labels of a segmentation checkpoint -> .npy
 score      confusion matrix / per-class IoU / mIoU of a segmentation checkpoint against true labels
+features   the feature instances (connected components of the labels) of a segmentation checkpoint -> JSON
 extend     ``PledgeEvolution.end2end`` (FM template -> B x C)
 sample     ``run_pledge`` (native diverse product sampler)
 template   write the built-in 1-block search-space FM
@@ -232,6 +233,25 @@ def cmd_score(a) -> int:
     return 0
 
 
+def cmd_features(a) -> int:
+    import numpy as np
+
+    from . import api
+
+    x = np.load(a.input, allow_pickle=False)
+    feats, ids = api.extract_features(a.model, x, packed_size=a.packed_size,
+                                      background=None if a.background < 0 else a.background,
+                                      connectivity=a.connectivity, min_voxels=a.min_voxels, return_ids=bool(a.ids))
+    if a.ids:
+        np.save(a.ids, ids)
+    summary = json.dumps({"samples": [[f.to_dict() for f in fs] for fs in feats]})
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(summary + "\n")
+    print(summary)
+    return 0
+
+
 def cmd_extend(a) -> int:
     from .fm.extend import generate_featuretree
 
@@ -383,6 +403,19 @@ def build_parser() -> argparse.ArgumentParser:
     sc.add_argument("--packed-size", type=int, default=None)
     sc.add_argument("--json", default="", metavar="OUT", help="also write the summary to this file")
     sc.set_defaults(fn=cmd_score)
+
+    ft = sub.add_parser("features", help="feature instances (connected components of the labels) of a "
+                                         "segmentation checkpoint")
+    ft.add_argument("model")
+    ft.add_argument("input", help="voxels (.npy), as for segment")
+    ft.add_argument("--json", default="", metavar="OUT", help="also write the JSON document to this file")
+    ft.add_argument("--ids", default="", metavar="IDS.npy", help="also write the instance-id volume (int32 .npy)")
+    ft.add_argument("--background", type=int, default=0, metavar="B",
+                    help="class that forms no instance (default 0; -1: every class does)")
+    ft.add_argument("--connectivity", type=int, default=6, choices=(6, 26))
+    ft.add_argument("--min-voxels", type=int, default=1, metavar="K", help="leave out smaller instances")
+    ft.add_argument("--packed-size", type=int, default=None)
+    ft.set_defaults(fn=cmd_features)
 
     e = sub.add_parser("extend", help="expand the 1-block template to B x C")
     e.add_argument("--input", default="")

@@ -40,6 +40,11 @@ int fn_pw_argmax(const void*, const void*, const float*, void*, void*, long long
 int fn_pw_argmax_cm_blocks(long long, int, int);
 int fn_pw_argmax_cm(const void*, const void*, const float*, const void*, void*, void*, void*, long long, int, int, int,
                     const float*, const float*, int, hipStream_t);
+void fn_ccl_tile(int*);
+int fn_ccl_local(const void*, void*, int, int, int, int, int, int, hipStream_t);
+int fn_ccl_merge(const void*, void*, int, int, int, int, int, int, hipStream_t);
+int fn_ccl_flatten(void*, void*, int, int, int, int, hipStream_t);
+int fn_ccl_stats(const void*, const void*, const void*, void*, void*, int, int, int, int, long long, hipStream_t);
 int fn_pw_wgrad(const void*, const void*, float*, long long, int, int, hipStream_t, const float*, const float*, int,
                 float*);
 int fn_pw_wgrad_blocks(long long, int, int);
@@ -656,6 +661,53 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("truth"), py::arg("labels"), py::arg("part"), py::arg("acc"),
      py::arg("M"), py::arg("K"), py::arg("N"), py::arg("ignore"), py::arg("psc"), py::arg("psh"), py::arg("pact"),
      py::arg("st"), py::arg("ext"));
+  // connected components of a label volume (ccl.hip): labels uint8 [N][D][H][W]; roots / flags / rank / ids
+  // int32 of that shape; background -1 = none; connectivity 6 or 26.  ccl_local + ccl_merge + ccl_flatten,
+  // in this order, leave roots[v] = 1 + the smallest linear index of v's component (0: background) and
+  // flags[v] = (roots[v] == v + 1); ext = {numel(labels), numel(roots)} / {numel(roots), numel(flags)}
+  m.def("ccl_tile", []() {
+    int t[3];
+    fn_ccl_tile(t);
+    return py::make_tuple(t[0], t[1], t[2]);
+  });
+  m.def("ccl_local", [](uintptr_t labels, uintptr_t roots, int N, int D, int H, int W, int background,
+                        int connectivity, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "ccl_local", "labels");
+    fits(ext, 1, prod({N, D, H, W}), "ccl_local", "roots");
+    chk(fn_ccl_local(P<const void*>(labels), P<void*>(roots), N, D, H, W, background, connectivity, S(st)),
+        "ccl_local");
+  }, py::arg("labels"), py::arg("roots"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"),
+     py::arg("background"), py::arg("connectivity"), py::arg("st"), py::arg("ext"));
+  m.def("ccl_merge", [](uintptr_t labels, uintptr_t roots, int N, int D, int H, int W, int background,
+                        int connectivity, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "ccl_merge", "labels");
+    fits(ext, 1, prod({N, D, H, W}), "ccl_merge", "roots");
+    chk(fn_ccl_merge(P<const void*>(labels), P<void*>(roots), N, D, H, W, background, connectivity, S(st)),
+        "ccl_merge");
+  }, py::arg("labels"), py::arg("roots"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"),
+     py::arg("background"), py::arg("connectivity"), py::arg("st"), py::arg("ext"));
+  m.def("ccl_flatten", [](uintptr_t roots, uintptr_t flags, int N, int D, int H, int W, uintptr_t st,
+                          std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "ccl_flatten", "roots");
+    fits(ext, 1, prod({N, D, H, W}), "ccl_flatten", "flags");
+    chk(fn_ccl_flatten(P<void*>(roots), P<void*>(flags), N, D, H, W, S(st)), "ccl_flatten");
+  }, py::arg("roots"), py::arg("flags"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("st"),
+     py::arg("ext"));
+  // rank: inclusive prefix sum of flags over the flat batch (N*D*H*W < 2^31), T = its last element; table int64
+  // [T][13] (fully rewritten), ids 0 = not wanted; ext = {numel(labels), numel(roots), numel(rank), numel(ids),
+  // numel(table)}
+  m.def("ccl_stats", [](uintptr_t labels, uintptr_t roots, uintptr_t rank, uintptr_t ids, uintptr_t table, int N,
+                        int D, int H, int W, long long T, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "ccl_stats", "labels");
+    fits(ext, 1, prod({N, D, H, W}), "ccl_stats", "roots");
+    fits(ext, 2, prod({N, D, H, W}), "ccl_stats", "rank");
+    if (ids) fits(ext, 3, prod({N, D, H, W}), "ccl_stats", "ids");
+    fits(ext, 4, prod({T, 13}), "ccl_stats", "table");
+    chk(fn_ccl_stats(P<const void*>(labels), P<const void*>(roots), P<const void*>(rank), P<void*>(ids),
+                     P<void*>(table), N, D, H, W, T, S(st)),
+        "ccl_stats");
+  }, py::arg("labels"), py::arg("roots"), py::arg("rank"), py::arg("ids"), py::arg("table"), py::arg("N"),
+     py::arg("D"), py::arg("H"), py::arg("W"), py::arg("T"), py::arg("st"), py::arg("ext"));
   // part: fp32 scratch of pw_wgrad_blocks(M, K, N) x N x K floats (per-workgroup partials)
   m.def("pw_wgrad", [](uintptr_t dy, uintptr_t x, uintptr_t dw, long long M, int K, int N, uintptr_t st,
                        uintptr_t psc, uintptr_t psh, int pact, uintptr_t part, long long part_n) {

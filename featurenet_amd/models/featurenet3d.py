@@ -258,6 +258,25 @@ class FeatureNet3DSeg(nn.Module):
                                           ignore_index=ignore_index, acc=acc, want_labels=want_labels)
         return acc, (labels.reshape(yv.shape[:-1]) if labels is not None else None)
 
+    @torch.no_grad()
+    def instances(self, x: torch.Tensor, background: int | None = 0, connectivity: int = 6,
+                  want_ids: bool = False):
+        """The features in each sample: :meth:`predict`'s labels split into connected components
+        -> ``(table, offsets, ids or None)`` on the model's device.  ``table`` int64 ``[T, 13]``
+        has one row per component (``sample, class, voxels, root, z0, y0, x0, z1, y1, x1, sum_z,
+        sum_y, sum_x``, sorted by sample and first voxel), sample ``n`` owns rows
+        ``offsets[n]:offsets[n + 1]``, ``ids`` int32 ``[N, S, S, S]`` numbers each sample's
+        components from 1 (``ops.ccl``).  Voxels of class ``background`` (None: no such class)
+        belong to no component; ``connectivity`` is 6 or 26.  The labels never leave the device."""
+        from ..ops import ccl
+
+        if connectivity not in (6, 26):
+            raise ValueError(f"instances: connectivity must be 6 or 26, not {connectivity!r}")
+        labels = self.predict(x)
+        roots, flags = ccl.connected_components(labels, background, connectivity, return_flags=True)
+        ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids, flags=flags)
+        return table, offsets, ids
+
     def loss(self, x: torch.Tensor, labels: torch.Tensor, smoothing: float = 0.0, with_correct: bool = False):
         """Mean per-voxel softmax cross-entropy against ``labels`` [N, S, S, S] (+ the number of
         top-1 hits when ``with_correct``).  Training on the GPU's sub-pixel path computes the loss

@@ -143,3 +143,90 @@ def confusion(truth: torch.Tensor, pred: torch.Tensor, n_classes: int, ignore_in
         t, p = t[keep], p[keep]
     key = torch.where(t >= n, torch.full_like(t, n * n), t * n + p)
     return torch.bincount(key, minlength=n * n + 1)
+
+
+def _ccl_offsets(connectivity: int) -> list[tuple[int, int, int]]:
+    if connectivity not in (6, 26):
+        raise ValueError(f"connectivity must be 6 (faces) or 26 (faces, edges and corners), not {connectivity!r}")
+    offs = [(dz, dy, dx) for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if (dz, dy, dx) != (0, 0, 0)]
+    return offs if connectivity == 26 else [o for o in offs if sum(map(abs, o)) == 1]
+
+
+def connected_components(labels: torch.Tensor, background: int | None = 0, connectivity: int = 6) -> torch.Tensor:
+    """Connected components of a label volume ``uint8 [N, D, H, W]`` -> ``roots`` int32 of the same
+    shape: 1 + the smallest C-order linear index (within the sample) of any voxel of the component,
+    0 for voxels of class ``background`` (None: every class forms components).  Two voxels of one
+    class are linked when they are 6- or 26-neighbours; nothing links across samples or wraps
+    round a row or plane.
+
+    Neighbour-min propagation over shifted views to a fixed point (every voxel keeps taking the
+    smallest value among itself and its linked neighbours, and then the value its own value's
+    voxel holds, until a sweep changes nothing): no union-find, the oracle of the ``ccl_*``
+    kernels and the CPU path of ``ops.ccl.connected_components``."""
+    offs = _ccl_offsets(connectivity)
+    if labels.dim() != 4 or labels.dtype != torch.uint8:
+        raise ValueError(f"connected_components: labels must be uint8 [N, D, H, W], not {labels.dtype} "
+                         f"{tuple(labels.shape)}")
+    N, D, H, W = labels.shape
+    V = D * H * W
+    if V >= 1 << 31:
+        raise ValueError("connected_components: a sample must have fewer than 2^31 voxels")
+    fg = torch.ones_like(labels, dtype=torch.bool) if background is None else labels != int(background)
+    cur = torch.where(fg, torch.arange(1, V + 1, device=labels.device).view(1, D, H, W), 0)
+    links = []
+    for dz, dy, dx in offs:
+        def sl(n, d):                            # (destination, source) slices of one axis
+            return (slice(max(0, -d), n - max(0, d)), slice(max(0, d), n - max(0, -d)))
+        (zd, zs), (yd, ys), (xd, xs) = sl(D, dz), sl(H, dy), sl(W, dx)
+        dst, src = (slice(None), zd, yd, xd), (slice(None), zs, ys, xs)
+        ok = fg[dst] & (labels[dst] == labels[src])
+        if ok.any():
+            links.append((dst, src, ok))
+    while N and V:
+        before = cur.clone()
+        for dst, src, ok in links:
+            cur[dst] = torch.where(ok, torch.minimum(cur[dst], cur[src]), cur[dst])
+        if torch.equal(cur, before):
+            break
+        flat = cur.view(N, V)                    # then the value of the voxel my value names
+        cur = torch.where(flat > 0, flat.gather(1, (flat - 1).clamp_(min=0)), 0).view(N, D, H, W)
+    return cur.to(torch.int32)
+
+
+def instance_table(labels: torch.Tensor, roots: torch.Tensor, want_ids: bool = True):
+    """Instance table of a labelled volume -> ``(ids or None, table, offsets)``.
+
+    ``roots`` as :func:`connected_components` gives them.  ``ids`` int32 ``[N, D, H, W]`` numbers
+    the components of each sample 1..n in ascending order of their root (0: background).
+    ``table`` int64 ``[T, 13]``, rows sorted by (sample, root), columns ``sample, class, voxels,
+    root, z0, y0, x0, z1, y1, x1`` (bounds inclusive), ``sum_z, sum_y, sum_x``; ``offsets`` int64
+    ``[N + 1]``: sample ``n`` owns rows ``offsets[n]:offsets[n + 1]``.  Exact integers: the oracle
+    of ``ccl_stats`` and the CPU path of ``ops.ccl.instance_table``."""
+    N, D, H, W = labels.shape
+    V = D * H * W
+    dev = labels.device
+    r = roots.reshape(N, V).to(torch.int64)
+    flags = r == torch.arange(1, V + 1, device=dev)
+    rank = torch.cumsum(flags.reshape(-1), 0).view(N, V)            # 1-based table row of each root
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), rank[:, -1]]) if V else \
+        torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    T = int(offsets[-1])
+    fg = r > 0
+    row = torch.where(fg, rank.gather(1, (r - 1).clamp_(min=0)), 0)   # 1-based row of every voxel
+    ids = None
+    if want_ids:
+        ids = torch.where(fg, row - offsets[:-1, None], 0).to(torch.int32).view(N, D, H, W)
+    table = torch.zeros(T, 13, dtype=torch.int64, device=dev)
+    if T:
+        n, v = fg.nonzero(as_tuple=True)
+        k = row[n, v] - 1
+        z, y, x = v // (H * W), v // W % H, v % W
+        table[:, 2] = torch.bincount(k, minlength=T)
+        first = flags[n, v]                                         # the root voxels, in row order
+        table[:, 0], table[:, 3] = n[first], v[first] + 1
+        table[:, 1] = labels.reshape(N, V)[n, v][first].to(torch.int64)
+        for c, q in enumerate((z, y, x)):
+            table[:, 4 + c] = torch.full((T,), 1 << 31, dtype=torch.int64, device=dev).scatter_reduce(0, k, q, "amin")
+            table[:, 7 + c] = torch.full((T,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, k, q, "amax")
+            table[:, 10 + c] = torch.zeros(T, dtype=torch.int64, device=dev).index_add_(0, k, q)
+    return ids, table, offsets
