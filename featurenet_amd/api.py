@@ -1,6 +1,6 @@
 """Public Python API: ``train()``, ``classify()``, ``segment()``, ``extract_features()``,
-``label_components()``, ``evaluate()``, ``evaluate_segmentation()``, ``load()``, ``save()``,
-``build_model()`` and ``search()``.
+``label_components()``, ``evaluate()``, ``evaluate_segmentation()``, ``evaluate_features()``,
+``match_features()``, ``load()``, ``save()``, ``build_model()`` and ``search()``.
 
 Reference parity: the de-facto entry point of the reference is the
 ``TensorflowGenerator(product, epochs, dataset, ...)`` constructor
@@ -349,6 +349,87 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     roots, flags = ccl.connected_components(lt, background, connectivity, return_flags=True)
     ids, table, offsets = ccl.instance_table(lt, roots, want_ids=True, flags=flags)
     return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets)
+
+
+def _label_volumes(labels, what: str, name: str = "labels") -> torch.Tensor:
+    lt = torch.as_tensor(np.asarray(labels)) if not isinstance(labels, torch.Tensor) else labels
+    if lt.is_floating_point() or lt.dtype == torch.bool:
+        raise ValueError(f"{what}: {name} must be integers, not {lt.dtype}")
+    if lt.dim() != 4:
+        raise ValueError(f"{what}: {name} must be [N, D, H, W], not {tuple(lt.shape)}")
+    if lt.dtype != torch.uint8 and lt.numel() and not lt.is_cuda and (int(lt.min()) < 0 or int(lt.max()) > 255):
+        raise ValueError(f"{what}: label values must lie in 0..255")
+    return lt
+
+
+@torch.no_grad()
+def evaluate_features(model, x, y, batch_size: int = 32, device=None, packed_size: int | None = None,
+                      background: int | None = 0, connectivity: int = 6, iou_threshold: float = 0.5,
+                      min_voxels: int = 1):
+    """Score a segmentation model feature by feature -> :class:`FeatureScore` (per class TP / FP /
+    FN, precision, recall, F1, segmentation / recognition / panoptic quality, and the matches).
+
+    ``model`` and ``x`` as for :func:`segment`, ``y`` as for :func:`evaluate_segmentation`;
+    ``background`` and ``connectivity`` as for :func:`extract_features`.  Runs
+    ``FeatureNet3DSeg.match``: the predicted labels and ``y`` are split into instances and the
+    shared voxels of every pair are counted on the model's device; only the two instance tables
+    and the overlap table cross to the host.  A predicted and a true instance of one class match
+    when their IoU exceeds ``iou_threshold`` (0.5 <= threshold < 1: above one half a match is
+    unique); instances of fewer than ``min_voxels`` voxels, on either side, count nowhere.  The
+    per-class arrays reach up to the largest class that occurs, as :func:`match_features`' do.
+    """
+    from .utils.featscore import FeatureScore
+
+    if isinstance(model, (str, Path)):
+        model, _ = load(model, device)
+    if not isinstance(model, FeatureNet3DSeg):
+        raise ValueError(f"evaluate_features() takes a FeatureNet3DSeg model, not {type(model).__name__} "
+                         "(see evaluate())")
+    if connectivity not in (6, 26):
+        raise ValueError(f"evaluate_features(): connectivity must be 6 or 26, not {connectivity!r}")
+    dev = next(model.parameters()).device
+    model.eval()
+    from .training.data import unpack_voxels
+
+    xt = torch.as_tensor(np.asarray(x)) if not isinstance(x, torch.Tensor) else x
+    yt = _label_volumes(y, "evaluate_features()")
+    if len(yt) != len(xt):
+        raise ValueError(f"evaluate_features(): {len(xt)} samples but {len(yt)} label volumes")
+    scores = []
+    for i in range(0, len(xt), batch_size):
+        xb = xt[i:i + batch_size].to(dev)
+        if packed_size is not None:
+            xb = unpack_voxels(xb, packed_size)
+        xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
+        five = model.match(xb, yt[i:i + batch_size].to(dev).to(torch.uint8), background=background,
+                           connectivity=connectivity)
+        scores.append(FeatureScore.from_tables(*five, iou_threshold=iou_threshold, min_voxels=min_voxels))
+    return FeatureScore.merge(scores)
+
+
+@torch.no_grad()
+def match_features(pred_labels, true_labels, background: int | None = 0, connectivity: int = 6,
+                   iou_threshold: float = 0.5, min_voxels: int = 1, device=None):
+    """:func:`evaluate_features` for label volumes the caller already has -> :class:`FeatureScore`.
+
+    ``pred_labels`` and ``true_labels`` are ``[N, D, H, W]`` of one shape, any integer dtype with
+    values 0..255.  ``device`` defaults to the GPU when there is one (the ``ccl`` and ``overlap``
+    kernels), else the CPU reference path.
+    """
+    from .ops import overlap
+    from .utils.featscore import FeatureScore
+
+    pt = _label_volumes(pred_labels, "match_features()", "pred_labels")
+    tt = _label_volumes(true_labels, "match_features()", "true_labels")
+    if pt.shape != tt.shape:
+        raise ValueError(f"match_features(): predicted labels are {tuple(pt.shape)} but true labels {tuple(tt.shape)}")
+    if connectivity not in (6, 26):
+        raise ValueError(f"match_features(): connectivity must be 6 or 26, not {connectivity!r}")
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    five = overlap.instance_overlap(pt.to(device).to(torch.uint8), tt.to(device).to(torch.uint8), background,
+                                    connectivity)
+    return FeatureScore.from_tables(*five, iou_threshold=iou_threshold, min_voxels=min_voxels)
 
 
 def evaluate(model, x, y, batch_size: int = 256, packed_size: int | None = None) -> float:

@@ -16,6 +16,8 @@ classify   load a checkpoint and predict (npy / binvox folder)
 segment    per-voxel labels of a segmentation checkpoint -> .npy
 score      confusion matrix / per-class IoU / mIoU of a segmentation checkpoint against true labels
 features   the feature instances (connected components of the labels) of a segmentation checkpoint -> JSON
+score-features
+           predicted features matched to the true ones: per-class TP / FP / FN, F1 and panoptic quality
 extend     ``PledgeEvolution.end2end`` (FM template -> B x C)
 sample     ``run_pledge`` (native diverse product sampler)
 template   write the built-in 1-block search-space FM
@@ -252,6 +254,24 @@ def cmd_features(a) -> int:
     return 0
 
 
+def cmd_score_features(a) -> int:
+    import numpy as np
+
+    from . import api
+
+    x = np.load(a.input, allow_pickle=False)
+    y = np.load(a.truth, allow_pickle=False)
+    score = api.evaluate_features(a.model, x, y, packed_size=a.packed_size,
+                                  background=None if a.background < 0 else a.background,
+                                  connectivity=a.connectivity, iou_threshold=a.iou, min_voxels=a.min_voxels)
+    summary = json.dumps(score.to_dict())
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(summary + "\n")
+    print(summary)
+    return 0
+
+
 def cmd_extend(a) -> int:
     from .fm.extend import generate_featuretree
 
@@ -416,6 +436,21 @@ def build_parser() -> argparse.ArgumentParser:
     ft.add_argument("--min-voxels", type=int, default=1, metavar="K", help="leave out smaller instances")
     ft.add_argument("--packed-size", type=int, default=None)
     ft.set_defaults(fn=cmd_features)
+
+    sf = sub.add_parser("score-features", help="match the predicted feature instances of a segmentation checkpoint "
+                                               "to the true ones: per-class TP / FP / FN, F1, panoptic quality")
+    sf.add_argument("model")
+    sf.add_argument("input", help="voxels (.npy), as for segment")
+    sf.add_argument("truth", help="true labels, integer [N, S, S, S] (.npy)")
+    sf.add_argument("--json", default="", metavar="OUT", help="also write the summary to this file")
+    sf.add_argument("--iou", type=float, default=0.5, metavar="T",
+                    help="a pair matches when its IoU exceeds T (0.5 <= T < 1)")
+    sf.add_argument("--min-voxels", type=int, default=1, metavar="K", help="leave out smaller instances on both sides")
+    sf.add_argument("--connectivity", type=int, default=6, choices=(6, 26))
+    sf.add_argument("--background", type=int, default=0, metavar="B",
+                    help="class that forms no instance (default 0; -1: every class does)")
+    sf.add_argument("--packed-size", type=int, default=None)
+    sf.set_defaults(fn=cmd_score_features)
 
     e = sub.add_parser("extend", help="expand the 1-block template to B x C")
     e.add_argument("--input", default="")

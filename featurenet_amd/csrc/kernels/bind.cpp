@@ -45,6 +45,9 @@ int fn_ccl_local(const void*, void*, int, int, int, int, int, int, hipStream_t);
 int fn_ccl_merge(const void*, void*, int, int, int, int, int, int, hipStream_t);
 int fn_ccl_flatten(void*, void*, int, int, int, int, hipStream_t);
 int fn_ccl_stats(const void*, const void*, const void*, void*, void*, int, int, int, int, long long, hipStream_t);
+void fn_overlap_chunk(int*);
+int fn_overlap_pairs(const void*, const void*, const void*, const void*, void*, void*, void*, int, long long, int,
+                     long long, long long, hipStream_t);
 int fn_pw_wgrad(const void*, const void*, float*, long long, int, int, hipStream_t, const float*, const float*, int,
                 float*);
 int fn_pw_wgrad_blocks(long long, int, int);
@@ -708,6 +711,32 @@ PYBIND11_MODULE(_C, m) {
         "ccl_stats");
   }, py::arg("labels"), py::arg("roots"), py::arg("rank"), py::arg("ids"), py::arg("table"), py::arg("N"),
      py::arg("D"), py::arg("H"), py::arg("W"), py::arg("T"), py::arg("st"), py::arg("ext"));
+  // overlap table of two id volumes (overlap.hip): ids_a / ids_b int32 [N*V] (per-sample ids from 1, 0 = none),
+  // off_a / off_b int64 [N+1] (the instance tables' offsets), keys uint64 [cap] / counts int64 [cap] / lost int64
+  // [1], all three zero on entry; cap a power of two, an update probes min(cap, probe) slots and is counted in
+  // lost when none is free; ext = {numel(ids_a), numel(ids_b), numel(off_a), numel(off_b), numel(keys),
+  // numel(counts), numel(lost)}
+  m.def("overlap_chunk", []() {
+    int t[2];
+    fn_overlap_chunk(t);
+    return py::make_tuple(t[0], t[1]);
+  });
+  m.def("overlap_pairs", [](uintptr_t ids_a, uintptr_t ids_b, uintptr_t off_a, uintptr_t off_b, uintptr_t keys,
+                            uintptr_t counts, uintptr_t lost, int N, long long V, int W, long long cap,
+                            long long probe, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, V}), "overlap_pairs", "ids_a");
+    fits(ext, 1, prod({N, V}), "overlap_pairs", "ids_b");
+    fits(ext, 2, N + 1LL, "overlap_pairs", "off_a");
+    fits(ext, 3, N + 1LL, "overlap_pairs", "off_b");
+    fits(ext, 4, cap, "overlap_pairs", "keys");
+    fits(ext, 5, cap, "overlap_pairs", "counts");
+    fits(ext, 6, 1, "overlap_pairs", "lost");
+    chk(fn_overlap_pairs(P<const void*>(ids_a), P<const void*>(ids_b), P<const void*>(off_a), P<const void*>(off_b),
+                         P<void*>(keys), P<void*>(counts), P<void*>(lost), N, V, W, cap, probe, S(st)),
+        "overlap_pairs");
+  }, py::arg("ids_a"), py::arg("ids_b"), py::arg("off_a"), py::arg("off_b"), py::arg("keys"), py::arg("counts"),
+     py::arg("lost"), py::arg("N"), py::arg("V"), py::arg("W"), py::arg("cap"), py::arg("probe"), py::arg("st"),
+     py::arg("ext"));
   // part: fp32 scratch of pw_wgrad_blocks(M, K, N) x N x K floats (per-workgroup partials)
   m.def("pw_wgrad", [](uintptr_t dy, uintptr_t x, uintptr_t dw, long long M, int K, int N, uintptr_t st,
                        uintptr_t psc, uintptr_t psh, int pact, uintptr_t part, long long part_n) {

@@ -1,0 +1,128 @@
+// Overlap table of two instance-id volumes (the step between the instance tables of ccl.hip and the
+// feature-level score): for every pair (instance a of volume A, instance b of volume B) that shares
+// a voxel, the number of shared voxels.
+//
+// ids_a, ids_b int32 [N*V]: per-sample ids from 1, 0 = none, as ccl_stats_kernel writes them;
+// off_a, off_b int64 [N+1]: the row range of each sample in the two instance tables.  A voxel g of
+// sample n with both ids > 0 lies in the 1-based global rows ra = off_a[n] + ids_a[g] and rb =
+// off_b[n] + ids_b[g]; its key is ra << 32 | rb (never 0, distinct across samples).  The result is
+// an open-addressing hash table keys uint64 [cap] (0 = empty) / counts int64 [cap], cap a power of
+// two, which the caller has zeroed: the SET of (key, count) pairs in it is exact and does not
+// depend on the order of the atomics; their slots do, so the caller sorts the occupied ones.
+#include "common.h"
+
+constexpr int OVL_NTHR = 256;
+constexpr int OVL_CHUNK = 16 * OVL_NTHR;        // voxels per workgroup
+constexpr int OVL_SLOTS = 512;                  // LDS (key, count) rows, entered at the key's hash
+constexpr int OVL_LPROBE = 8;                   // LDS slots an update tries before it goes to global memory
+static_assert((OVL_SLOTS & (OVL_SLOTS - 1)) == 0 && OVL_NTHR % FN_WAVE == 0, "table shape");
+
+#define OVL_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
+
+// The 64-bit finalizer of MurmurHash3: every output bit depends on every key bit.  The top 9 bits
+// pick the LDS slot, the low bits (cap <= 2^32) the global one.  A single multiplication is not
+// enough: the keys are pairs of small, correlated row numbers (rb = ra + d for a prediction close
+// to the truth), and its middle bits put them in clusters -- 12 probes per insert at load 0.4
+// where this gives 0.35, as random keys do.
+__device__ __forceinline__ unsigned long long ovl_mix(unsigned long long k) {
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33;
+  k *= 0xc4ceb9fe1a85ec53ull;
+  k ^= k >> 33;
+  return k;
+}
+
+// counts[slot of key] += cnt.  Linear probing from the key's home slot, at most `bound` (<= cap)
+// slots: a returning compare-and-swap claims an empty slot or shows whose it is.  An update that
+// finds neither its key nor an empty slot within the bound is dropped and its voxels counted in
+// lost[0] (the caller grows the table and runs again).  Nothing here waits for another thread.
+__device__ __forceinline__ void ovl_global_add(unsigned long long* keys, long long* counts, long long* lost,
+                                               unsigned long long mask, long long bound, unsigned long long key,
+                                               long long cnt) {
+  unsigned long long h = ovl_mix(key) & mask;
+  for (long long i = 0; i < bound; ++i) {
+    unsigned long long held = 0;
+    __hip_atomic_compare_exchange_strong(&keys[h], &held, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+    if (held == 0 || held == key) {              // (held keeps 0 when the exchange was made)
+      __hip_atomic_fetch_add(&counts[h], cnt, OVL_RLX_AGENT);
+      return;
+    }
+    h = (h + 1) & mask;
+  }
+  __hip_atomic_fetch_add(lost, cnt, OVL_RLX_AGENT);
+}
+
+// One lane per voxel, OVL_CHUNK consecutive voxels (of the flat [N*V] range, < 2^31) per workgroup,
+// as ccl_stats_kernel.  A run of equal keys along a row of W (it breaks at lane 0, at x == 0 and
+// where either id changes) is one update of `len` voxels, made by its first lane; the updates of a
+// workgroup meet in the LDS table first, and each occupied slot makes one global update at the end:
+// two solid volumes make one global update per workgroup, not one per voxel.  An update whose
+// OVL_LPROBE slots from its hash on are all held by other keys goes to the global table directly;
+// that costs the wave a returning global atomic inside the loop, which a strictly direct-mapped
+// table (OVL_LPROBE = 1) pays on most rows already at ~130 keys per chunk (59 against 46 us on
+// the blobs of profiles/feature_match.md).
+__global__ __launch_bounds__(OVL_NTHR) void overlap_pairs_kernel(const int* __restrict__ ids_a,
+                                                                 const int* __restrict__ ids_b,
+                                                                 const long long* __restrict__ off_a,
+                                                                 const long long* __restrict__ off_b,
+                                                                 unsigned long long* keys, long long* counts,
+                                                                 long long* lost, int total, int V, int W,
+                                                                 unsigned long long mask, long long bound) {
+  __shared__ unsigned long long s_key[OVL_SLOTS];
+  __shared__ unsigned long long s_cnt[OVL_SLOTS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int s = tid; s < OVL_SLOTS; s += OVL_NTHR) s_key[s] = 0, s_cnt[s] = 0;
+  __syncthreads();
+  const int g0 = blockIdx.x * OVL_CHUNK;        // (total < 2^31 and the grid covers it: no overflow below)
+  for (int it = 0; it < OVL_CHUNK / OVL_NTHR; ++it) {
+    const unsigned gu = (unsigned)g0 + (unsigned)(it * OVL_NTHR + tid);
+    const bool valid = gu < (unsigned)total;
+    const int g = valid ? (int)gu : total - 1;
+    const int n = g / V, x = (g - n * V) % W;
+    const int a = ids_a[g], b = ids_b[g];
+    const bool on = valid && a > 0 && b > 0;
+    const unsigned long long ra = (unsigned long long)(off_a[n] + a), rb = (unsigned long long)(off_b[n] + b);
+    const unsigned long long key = on ? (ra << 32) | (rb & 0xffffffffull) : 0ull;
+    const unsigned long long prev = __shfl_up(key, 1, 64);
+    const unsigned long long heads = __ballot(lane == 0 || x == 0 || key != prev);
+    const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
+    const int len = (above ? __builtin_ctzll(above) : 64) - lane;
+    if (((heads >> lane) & 1) && key != 0) {
+      int slot = (int)(ovl_mix(key) >> 55) & (OVL_SLOTS - 1);
+      bool met = false;
+      for (int p = 0; p < OVL_LPROBE && !met; ++p) {
+        const unsigned long long held = atomicCAS(&s_key[slot], 0ull, key);
+        met = held == 0 || held == key;
+        if (met) atomicAdd(&s_cnt[slot], (unsigned long long)len);
+        slot = (slot + 1) & (OVL_SLOTS - 1);
+      }
+      if (!met) ovl_global_add(keys, counts, lost, mask, bound, key, len);
+    }
+  }
+  __syncthreads();
+  for (int s = tid; s < OVL_SLOTS; s += OVL_NTHR)
+    if (s_key[s] != 0) ovl_global_add(keys, counts, lost, mask, bound, s_key[s], (long long)s_cnt[s]);
+}
+
+extern "C" void fn_overlap_chunk(int* t) { t[0] = OVL_CHUNK, t[1] = OVL_SLOTS; }
+
+// keys uint64 [cap], counts int64 [cap] and lost int64 [1] are zero on entry (a key or count left
+// from an earlier call is added to).  cap: a power of two in [2, 2^32]; probe >= 1: an update gives
+// up (-> lost) after min(cap, probe) slots.  W: the row length, V = D*H*W voxels per sample.
+extern "C" int fn_overlap_pairs(const void* ids_a, const void* ids_b, const void* off_a, const void* off_b,
+                                void* keys, void* counts, void* lost, int N, long long V, int W, long long cap,
+                                long long probe, hipStream_t st) {
+  if (!ids_a || !ids_b || !off_a || !off_b || !keys || !counts || !lost) return -2;
+  if (N < 1 || V < 1 || W < 1 || V % W != 0) return -2;
+  if (cap < 2 || cap > (1LL << 32) || (cap & (cap - 1)) != 0 || probe < 1) return -2;
+  if (V >= (1LL << 31) || V * N >= (1LL << 31)) return -2;
+  const long long total = V * N;
+  hipLaunchKernelGGL(overlap_pairs_kernel, dim3((unsigned)((total + OVL_CHUNK - 1) / OVL_CHUNK)), dim3(OVL_NTHR), 0,
+                     st, (const int*)ids_a, (const int*)ids_b, (const long long*)off_a, (const long long*)off_b,
+                     (unsigned long long*)keys, (long long*)counts, (long long*)lost, (int)total, (int)V, W,
+                     (unsigned long long)(cap - 1), probe < cap ? probe : cap);
+  FN_CHECK_LAUNCH();
+  return 0;
+}

@@ -277,6 +277,25 @@ class FeatureNet3DSeg(nn.Module):
         ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids, flags=flags)
         return table, offsets, ids
 
+    def match(self, x: torch.Tensor, y: torch.Tensor, background: int | None = 0, connectivity: int = 6):
+        """The predicted features against the true ones: the instances of :meth:`predict`'s labels,
+        the instances of ``y`` (true labels, uint8 ``[N, S, S, S]`` on the model's device) and the
+        overlap table of the two -> ``(table_pred, off_pred, table_true, off_true, pairs)`` on the
+        model's device.  Tables and offsets as :meth:`instances` gives them; ``pairs`` int64 ``[P,
+        3]`` has one row ``(row_pred, row_true, shared voxels)`` per pair of instances that touch
+        (``ops.overlap``).  ``utils.featscore`` turns the five into matches and a score.  No
+        per-voxel tensor leaves the device."""
+        from ..ops import overlap
+
+        if connectivity not in (6, 26):
+            raise ValueError(f"match: connectivity must be 6 or 26, not {connectivity!r}")
+        labels = self.predict(x)
+        if not isinstance(y, torch.Tensor) or y.dtype != torch.uint8 or y.shape != labels.shape \
+                or y.device != labels.device:
+            got = f"{y.dtype} {tuple(y.shape)} on {y.device}" if isinstance(y, torch.Tensor) else type(y).__name__
+            raise ValueError(f"match: y must be uint8 {tuple(labels.shape)} on {labels.device}, not {got}")
+        return overlap.instance_overlap(labels, y, background, connectivity)
+
     def loss(self, x: torch.Tensor, labels: torch.Tensor, smoothing: float = 0.0, with_correct: bool = False):
         """Mean per-voxel softmax cross-entropy against ``labels`` [N, S, S, S] (+ the number of
         top-1 hits when ``with_correct``).  Training on the GPU's sub-pixel path computes the loss

@@ -230,3 +230,21 @@ def instance_table(labels: torch.Tensor, roots: torch.Tensor, want_ids: bool = T
             table[:, 7 + c] = torch.full((T,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, k, q, "amax")
             table[:, 10 + c] = torch.zeros(T, dtype=torch.int64, device=dev).index_add_(0, k, q)
     return ids, table, offsets
+
+
+def overlap_table(ids_a: torch.Tensor, off_a: torch.Tensor, ids_b: torch.Tensor, off_b: torch.Tensor) -> torch.Tensor:
+    """Overlap table of two instance-id volumes -> ``pairs`` int64 ``[P, 3]``.
+
+    ``ids_a`` / ``ids_b`` int32 ``[N, D, H, W]`` and ``off_a`` / ``off_b`` int64 ``[N + 1]`` as
+    :func:`instance_table` gives them for two label volumes of one shape.  One row ``(row_a, row_b,
+    voxels)`` per pair of instances that share a voxel: their 0-based rows in the two instance
+    tables and the number of shared voxels, sorted by ``(row_a, row_b)``.  Exact integers: the
+    oracle of ``overlap_pairs`` and the CPU path of ``ops.overlap.overlap_table``."""
+    N = ids_a.shape[0]
+    a = ids_a.reshape(N, -1).to(torch.int64)
+    b = ids_b.reshape(N, -1).to(torch.int64)
+    both = (a > 0) & (b > 0)
+    ra = a + off_a.to(torch.int64)[:-1, None] - 1
+    rb = b + off_b.to(torch.int64)[:-1, None] - 1
+    keys, counts = torch.unique((ra << 32 | rb)[both], return_counts=True)
+    return torch.stack([keys >> 32, keys & 0xffffffff, counts], 1)
