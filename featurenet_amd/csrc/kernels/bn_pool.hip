@@ -1,20 +1,81 @@
 // BatchNorm(+activation) and pooling kernels, channels-last, bf16 I/O, fp32 math.
 //
-// Forward training path of a BN layer that follows an implicit-GEMM conv:
-//   conv epilogue -> per-block (sum, sumsq) slabs  (conv_igemm.hip, STATS=true)
-//   bn_finalize   -> mean / invstd / scale / shift + running-stat update
-//   bn_apply      -> z = act(y*scale + shift)          (or fused into pooling)
-// Backward:
-//   bn_bwd_reduce -> per-block (sum g, sum g*xhat) slabs, g = dz * act'(z)
-//   bn_finalize   -> dbeta / dgamma
-//   bn_bwd_apply  -> dy = gamma*invstd*(g - dbeta/M - xhat*dgamma/M)
+// Forward training path of a BN layer:
+//   conv epilogue, or colstats mode 0 -> per-block (sum, sumsq) slabs
+//   bn_finalize mode 0 -> mean / invstd / scale / shift + running-stat update
+//   bn_apply           -> z = act(y*scale + shift)     (or fused into pooling)
+// Backward, dy = gamma*invstd*(g - dbeta/M - xhat*dgamma/M) with g = dz * act'(z):
+//   colstats mode 1    -> per-block (sum g, sum g*xhat) slabs
+//   bn_finalize mode 1 -> dbeta / dgamma
+//   bn_bwd_apply       -> dy (bn_bwd_apply_s2d: in the sub-pixel decoder's shifted layout)
+// or, where a conv consumes z = relu(bn(y)), without the colstats pass (the statistics
+// identity): bn_wdot + bn_bwd_prep -> apply constants, bn_bwd_apply_k -> dy and dgamma.
 // MaxPool/AvgPool take an optional BN+act prologue so the normalised
 // activation of the layer feeding a pool is never written to HBM
-// (FeatureNet-3D conv4 -> BN -> ReLU -> MaxPool3d is one read of y4).
+// (FeatureNet-3D conv4 -> BN -> ReLU -> MaxPool3d is one read of y4); the max-pool
+// backward of such a block gives the BN's raw moments (pool_bwd_stats, bn_finalize mode 2)
+// and its dy in one pass (pool_bn_bwd_apply).
 #include "common.h"
 
 #include <algorithm>
 #include <type_traits>
+
+// ---------------------------------------------------------------------------
+// Parts shared by the kernels below.  Expression order is part of their contract: fp32 is not
+// associative and hipcc contracts to FMA per expression.
+// ---------------------------------------------------------------------------
+// Block reduction of per-thread moments (s0, s1) of VW channels into part[block][2][C]: thread
+// t < rpp * cpr (the active ones) holds chunk t % cpr (cpr = C / VW chunks, rpp = 256 / cpr); one
+// thread per channel sums the rpp partials that share its chunk, ascending t.
+template <int VW>
+__device__ __forceinline__ void block_moments_to_part(const float (&s0)[VW], const float (&s1)[VW], bool active, int C,
+                                                      float* __restrict__ part) {
+  __shared__ float red[256][2 * VW + 1];
+  const int tid = threadIdx.x;
+  const int cpr = C / VW, rpp = 256 / cpr;
+#pragma unroll
+  for (int j = 0; j < VW; ++j) { red[tid][j] = active ? s0[j] : 0.f; red[tid][VW + j] = active ? s1[j] : 0.f; }
+  __syncthreads();
+  for (int c = tid; c < C; c += 256) {
+    const int chk = c / VW, j = c % VW;
+    float a = 0.f, b = 0.f;
+    for (int i = 0; i < rpp; ++i) { a += red[i * cpr + chk][j]; b += red[i * cpr + chk][VW + j]; }
+    part[(long long)blockIdx.x * 2 * C + c] = a;
+    part[(long long)blockIdx.x * 2 * C + C + c] = b;
+  }
+}
+
+// BN backward's input gradient, dy = gamma*invstd*(g - dbeta/M - xhat*dgamma/M), g = dz*act'(z)
+//    = k1*g + k2*y + k3 per channel with k1 = scale,
+//      k2 = -scale*invstd*dgamma/M, k3 = -scale*(dbeta/M - mean*invstd*dgamma/M):
+// the constants of the VW channels from c0 on (and sc = scale, sh = shift, for z)
+template <int VW>
+__device__ __forceinline__ void bn_bwd_consts(int c0, const float* __restrict__ scale, const float* __restrict__ shift,
+                                              const float* __restrict__ mean, const float* __restrict__ invstd,
+                                              const float* __restrict__ dbeta, const float* __restrict__ dgamma,
+                                              float inv_count, float (&sc)[VW], float (&sh)[VW], float (&k2)[VW],
+                                              float (&k3)[VW]) {
+#pragma unroll
+  for (int j = 0; j < VW; ++j) {
+    const int c = c0 + j;
+    sc[j] = scale[c];
+    sh[j] = shift[c];
+    const float is = invstd[c];
+    k2[j] = -sc[j] * is * dgamma[c] * inv_count;
+    k3[j] = -sc[j] * (dbeta[c] * inv_count - mean[c] * is * dgamma[c] * inv_count);
+  }
+}
+
+// ... one element of it from g, and from dz (g = dz * act'(act(y*sc + sh)))
+__device__ __forceinline__ bf16 bn_bwd_dy_of_g(float yv, float g, float sc, float k2, float k3) {
+  return f2bf(sc * g + k2 * yv + k3);
+}
+
+__device__ __forceinline__ bf16 bn_bwd_dy(float yv, float dzv, float sc, float sh, float k2, float k3, int act) {
+  const float zv = act_fwd(yv * sc + sh, act);
+  const float g = dzv * act_bwd_from_out(zv, act);
+  return bn_bwd_dy_of_g(yv, g, sc, k2, k3);
+}
 
 // ---------------------------------------------------------------------------
 // Column statistics: per-block partial sums over rows of a [M][C] tensor.
@@ -29,7 +90,6 @@ __global__ __launch_bounds__(256) void colstats_kernel(const bf16* __restrict__ 
                                                        float* __restrict__ part, long long M, int C,
                                                        long long rows_per_block) {
   constexpr int act = ACT;          // compile-time activation: no per-element switch
-  __shared__ float red[256][2 * VW + 1];
   const int tid = threadIdx.x;
   const int cpr = C / VW;           // chunks per row
   const int rpp = 256 / cpr;        // rows per pass
@@ -82,17 +142,7 @@ __global__ __launch_bounds__(256) void colstats_kernel(const bf16* __restrict__ 
       }
     }
   }
-#pragma unroll
-  for (int j = 0; j < VW; ++j) { red[tid][j] = active ? s0[j] : 0.f; red[tid][VW + j] = active ? s1[j] : 0.f; }
-  __syncthreads();
-  // one thread per channel sums the rpp partials that share its chunk
-  for (int c = tid; c < C; c += 256) {
-    const int chk = c / VW, j = c % VW;
-    float a = 0.f, b = 0.f;
-    for (int i = 0; i < rpp; ++i) { a += red[i * cpr + chk][j]; b += red[i * cpr + chk][VW + j]; }
-    part[(long long)blockIdx.x * 2 * C + c] = a;
-    part[(long long)blockIdx.x * 2 * C + C + c] = b;
-  }
+  block_moments_to_part<VW>(s0, s1, active, C, part);
 }
 
 // Column sums (MODE 0) of a [M][C] tensor whose C is not a multiple of 8 (bias gradients of
@@ -256,9 +306,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16* __restrict__ 
   }
 }
 
-// dy = gamma*invstd*(g - dbeta/M - xhat*dgamma/M), g = dz*act'(z)
-//    = k1*g + k2*y + k3 per channel with k1 = scale,
-//      k2 = -scale*invstd*dgamma/M, k3 = -scale*(dbeta/M - mean*invstd*dgamma/M)
+// dy = k1*g + k2*y + k3 (bn_bwd_consts, bn_bwd_dy)
 template <int VW, int ACT>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16* __restrict__ dz, const bf16* __restrict__ y,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
@@ -273,15 +321,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16* __restric
   const bool fixed = (256 % cpr) == 0;
   float sc[VW], sh[VW], k2[VW], k3[VW];
   auto load_params = [&](int c0) {
-#pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      const int c = c0 + j;
-      sc[j] = scale[c];
-      sh[j] = shift[c];
-      const float is = invstd[c];
-      k2[j] = -sc[j] * is * dgamma[c] * inv_count;
-      k3[j] = -sc[j] * (dbeta[c] * inv_count - mean[c] * is * dgamma[c] * inv_count);
-    }
+    bn_bwd_consts<VW>(c0, scale, shift, mean, invstd, dbeta, dgamma, inv_count, sc, sh, k2, k3);
   };
   if (fixed) load_params((int)(threadIdx.x % cpr) * VW);
 #pragma unroll 2
@@ -296,12 +336,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16* __restric
       pd.e[0] = dz[i];
     }
 #pragma unroll
-    for (int j = 0; j < VW; ++j) {
-      const float yv = bf2f(py.e[j]);
-      const float zv = act_fwd(yv * sc[j] + sh[j], act);
-      const float g = bf2f(pd.e[j]) * act_bwd_from_out(zv, act);
-      po.e[j] = f2bf(sc[j] * g + k2[j] * yv + k3[j]);
-    }
+    for (int j = 0; j < VW; ++j) po.e[j] = bn_bwd_dy(bf2f(py.e[j]), bf2f(pd.e[j]), sc[j], sh[j], k2[j], k3[j], act);
     if constexpr (VW == 8) *(uint4*)(dy + i * 8) = po.u;
     else dy[i] = po.e[0];
   }
@@ -483,15 +518,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_s2d_kernel(const bf16* __res
   const long long i0 = blockIdx.x * 256LL + threadIdx.x;
   const int k = (int)(threadIdx.x % cpr);
   float sc[8], sh[8], k2[8], k3[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = k * 8 + j;
-    sc[j] = scale[c];
-    sh[j] = shift[c];
-    const float is = invstd[c];
-    k2[j] = -sc[j] * is * dgamma[c] * inv_count;
-    k3[j] = -sc[j] * (dbeta[c] * inv_count - mean[c] * is * dgamma[c] * inv_count);
-  }
+  bn_bwd_consts<8>(k * 8, scale, shift, mean, invstd, dbeta, dgamma, inv_count, sc, sh, k2, k3);
   for (long long i = i0; i < nvec; i += stride) {
     const long long s = i / cpr;
     const int jp = (int)(s & 7);
@@ -510,12 +537,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_s2d_kernel(const bf16* __res
       py.u = *(const uint4*)(y + off);
       pd.u = *(const uint4*)(dz + off);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float yv = bf2f(py.e[j]);
-        const float zv = act_fwd(yv * sc[j] + sh[j], act);
-        const float g = bf2f(pd.e[j]) * act_bwd_from_out(zv, act);
-        po.e[j] = f2bf(sc[j] * g + k2[j] * yv + k3[j]);
-      }
+      for (int j = 0; j < 8; ++j) po.e[j] = bn_bwd_dy(bf2f(py.e[j]), bf2f(pd.e[j]), sc[j], sh[j], k2[j], k3[j], act);
     } else {
       po.u = make_uint4(0u, 0u, 0u, 0u);
     }
@@ -545,15 +567,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_s2d_rows_kernel(const bf16* 
   const int D2 = FD / 2 + 1, H2 = FH / 2 + 1, W2 = FW / 2 + 1;
   const int k = (int)(threadIdx.x & (cpr - 1));   // (256 is a multiple of cpr: the chunk is fixed)
   float sc[8], sh[8], k2[8], k3[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = k * 8 + j;
-    sc[j] = scale[c];
-    sh[j] = shift[c];
-    const float is = invstd[c];
-    k2[j] = -sc[j] * is * dgamma[c] * inv_count;
-    k3[j] = -sc[j] * (dbeta[c] * inv_count - mean[c] * is * dgamma[c] * inv_count);
-  }
+  bn_bwd_consts<8>(k * 8, scale, shift, mean, invstd, dbeta, dgamma, inv_count, sc, sh, k2, k3);
   const int rowlen = W2 * 8 * cpr;
   const int nrows = N * D2 * H2;
   for (int row = blockIdx.x; row < nrows; row += gridDim.x) {
@@ -580,12 +594,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_s2d_rows_kernel(const bf16* 
         Pack8 po;
         if (in[u]) {
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float yv = bf2f(py[u].e[j]);
-            const float zv = act_fwd(yv * sc[j] + sh[j], act);
-            const float g = bf2f(pd[u].e[j]) * act_bwd_from_out(zv, act);
-            po.e[j] = f2bf(sc[j] * g + k2[j] * yv + k3[j]);
-          }
+          for (int j = 0; j < 8; ++j)
+            po.e[j] = bn_bwd_dy(bf2f(py[u].e[j]), bf2f(pd[u].e[j]), sc[j], sh[j], k2[j], k3[j], act);
         } else {
           po.u = make_uint4(0u, 0u, 0u, 0u);
         }
@@ -911,20 +921,32 @@ __global__ __launch_bounds__(256) void pool_bwd_tiled_kernel(const bf16* __restr
       }
     }
   }
-  if constexpr (STATS) {
-    __shared__ float red[256][2 * VW + 1];
-    const int tid = threadIdx.x;
+  if constexpr (STATS) block_moments_to_part<VW>(s0, s1, true, g.C, part);   // (256 % cpr == 0: all active)
+}
+
+// The two kernels below give one thread a non-overlapping window of <= 8 positions (host-checked)
+// of one 8-channel chunk ch, window i of the flat (n, od, oh, ow, chunk) order.  Their shared
+// parts (I = int: 32-bit index math, when the host checked that every offset fits):
+// offsets of the window's members from its origin (members past win repeat member 0)
+template <typename I>
+__device__ __forceinline__ void pool_win_offsets(const PoolGeom& g, int win, I (&wofs)[8]) {
 #pragma unroll
-    for (int j = 0; j < VW; ++j) { red[tid][j] = s0[j]; red[tid][VW + j] = s1[j]; }
-    __syncthreads();
-    for (int c = tid; c < g.C; c += 256) {       // thread t holds chunk t % cpr (256 % cpr == 0)
-      const int chk = c / VW, j = c % VW;
-      float a = 0.f, b = 0.f;
-      for (int t = chk; t < 256; t += cpr) { a += red[t][j]; b += red[t][VW + j]; }
-      part[(long long)blockIdx.x * 2 * g.C + c] = a;
-      part[(long long)blockIdx.x * 2 * g.C + g.C + c] = b;
-    }
+  for (int w = 0; w < 8; ++w) {
+    const int ww = w < win ? w : 0;
+    const int kw = ww % g.KW, kh = (ww / g.KW) % g.KH, kd = ww / (g.KW * g.KH);
+    wofs[w] = (((I)kd * g.H + kh) * g.W + kw) * g.C;
   }
+}
+
+// element offset of window ii's first member
+template <typename I>
+__device__ __forceinline__ I pool_win_origin(const PoolGeom& g, I ii, int cpr, int ch) {
+  I t = ii / cpr;
+  const int ow = (int)(t % g.OW); t /= g.OW;
+  const int oh = (int)(t % g.OH); t /= g.OH;
+  const int od = (int)(t % g.OD);
+  const I n = t / g.OD;
+  return (((n * g.D + (I)od * g.KD) * g.H + (I)oh * g.KH) * g.W + (I)ow * g.KW) * g.C + ch * 8;
 }
 
 // BN backward moments of a BN+act+max-pool block without writing dz (the fused apply below
@@ -950,23 +972,14 @@ __global__ __launch_bounds__(256) void pool_bn_moments8_kernel(const bf16* __res
     sh[j] = shift[ch * 8 + j];
     s0[j] = s1[j] = 0.f;
   }
-  I wofs[8];                                     // window member offsets from the window origin
-#pragma unroll
-  for (int w = 0; w < 8; ++w) {
-    const int ww = w < win ? w : 0;
-    const int kw = ww % g.KW, kh = (ww / g.KW) % g.KH, kd = ww / (g.KW * g.KH);
-    wofs[w] = (((I)kd * g.H + kh) * g.W + kw) * g.C;
-  }
+  I wofs[8];
+  pool_win_offsets<I>(g, win, wofs);
   // software-pipelined: the next window's 9 loads are issued before this one is reduced (an
   // index past the end re-loads the current window: unconditional loads, so hipcc's wait
-  // counts stay exact)
+  // counts stay exact).  The loads stay in each kernel: as a shared function they cost the
+  // long long instances here 3 VGPRs (127 -> 130).
   auto fetch = [&](I ii, Pack8& q, Pack8* qy) {
-    I t = ii / cpr;
-    const int ow = (int)(t % g.OW); t /= g.OW;
-    const int oh = (int)(t % g.OH); t /= g.OH;
-    const int od = (int)(t % g.OD);
-    const I n = t / g.OD;
-    const I b0 = (((n * g.D + (I)od * g.KD) * g.H + (I)oh * g.KH) * g.W + (I)ow * g.KW) * g.C + ch * 8;
+    const I b0 = pool_win_origin<I>(g, ii, cpr, ch);
     q.u = *(const uint4*)(dout + ii * 8);
 #pragma unroll
     for (int w = 0; w < 8; ++w)
@@ -1000,18 +1013,7 @@ __global__ __launch_bounds__(256) void pool_bn_moments8_kernel(const bf16* __res
     for (int w = 0; w < 8; ++w) py[w] = py2[w];
     i = inx;
   }
-  __shared__ float red[256][17];
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { red[tid][j] = s0[j]; red[tid][8 + j] = s1[j]; }
-  __syncthreads();
-  for (int c = tid; c < g.C; c += 256) {
-    const int chk = c / 8, j = c % 8;
-    float a = 0.f, b = 0.f;
-    for (int u = chk; u < 256; u += cpr) { a += red[u][j]; b += red[u][8 + j]; }
-    part[(long long)blockIdx.x * 2 * g.C + c] = a;
-    part[(long long)blockIdx.x * 2 * g.C + g.C + c] = b;
-  }
+  block_moments_to_part<8>(s0, s1, true, g.C, part);
 }
 
 // Max-pool backward and the BN backward's input gradient in one pass (non-overlapping windows
@@ -1037,30 +1039,10 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_apply_kernel(
   // host-checked): the per-channel constants are loaded once, not per window
   const int ch = (int)(threadIdx.x % cpr);
   float sc[8], sh[8], k2[8], k3[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = ch * 8 + j;
-    sc[j] = scale[c];
-    sh[j] = shift[c];
-    const float is = invstd[c];
-    k2[j] = -sc[j] * is * dgamma[c] * inv_count;
-    k3[j] = -sc[j] * (dbeta[c] * inv_count - mean[c] * is * dgamma[c] * inv_count);
-  }
-  I wofs[8];                                     // window member offsets from the window origin
-#pragma unroll
-  for (int w = 0; w < 8; ++w) {
-    const int ww = w < win ? w : 0;
-    const int kw = ww % g.KW, kh = (ww / g.KW) % g.KH, kd = ww / (g.KW * g.KH);
-    wofs[w] = (((I)kd * g.H + kh) * g.W + kw) * g.C;
-  }
-  auto origin = [&](I ii) -> I {
-    I t = ii / cpr;
-    const int ow = (int)(t % g.OW); t /= g.OW;
-    const int oh = (int)(t % g.OH); t /= g.OH;
-    const int od = (int)(t % g.OD);
-    const I n = t / g.OD;
-    return (((n * g.D + (I)od * g.KD) * g.H + (I)oh * g.KH) * g.W + (I)ow * g.KW) * g.C + ch * 8;
-  };
+  bn_bwd_consts<8>(ch * 8, scale, shift, mean, invstd, dbeta, dgamma, inv_count, sc, sh, k2, k3);
+  I wofs[8];
+  pool_win_offsets<I>(g, win, wofs);
+  auto origin = [&](I ii) -> I { return pool_win_origin<I>(g, ii, cpr, ch); };
   // software-pipelined as pool_bn_moments8_kernel: the next window's loads are in flight
   // while this one is reduced and stored
   auto fetch = [&](I ii, I b0, Pack8& q, Pack8* qy) {
@@ -1108,7 +1090,7 @@ __global__ __launch_bounds__(256) void pool_bn_bwd_apply_kernel(
         Pack8 po;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          po.e[j] = f2bf(sc[j] * (arg[j] == w ? gm[j] : 0.f) + k2[j] * bf2f(py[w].e[j]) + k3[j]);
+          po.e[j] = bn_bwd_dy_of_g(bf2f(py[w].e[j]), arg[j] == w ? gm[j] : 0.f, sc[j], k2[j], k3[j]);
         *(uint4*)(dy + b0 + wofs[w]) = po.u;
       }
     }
@@ -1134,35 +1116,73 @@ static int bn_resident_blocks(const void* kernel) {
   return cus > 0 && per > 0 ? cus * per : 0;
 }
 
-static unsigned ew_blocks(long long work) {
-  long long b = (work + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 8192) b = 8192;
-  return (unsigned)b;
+// The two grids of a grid-stride kernel that wants one resident wave of workgroups (res =
+// bn_resident_blocks of it, 0 when unknown): `blocks` clamped to res, then to [1, 8192] ...
+static unsigned resident_grid(long long blocks, int res) {
+  if (res > 0 && blocks > res) blocks = res;
+  return (unsigned)(blocks < 1 ? 1 : (blocks > 8192 ? 8192 : blocks));
+}
+
+static unsigned ew_blocks(long long work) { return resident_grid((work + 255) / 256, 0); }
+
+// ... and, where the blocks are the rows of a partial-sum slab: [1, res], or [1, 2048]
+static int resident_rows(long long blocks, int res) {
+  const long long cap = res > 0 ? res : 2048;
+  return (int)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+}
+
+// a thread of a 256-stride loop over 8-channel chunks keeps its chunk
+static bool chunk_fixed(int C) { return C % 8 == 0 && 256 % (C / 8) == 0; }
+
+// Runtime value -> template argument: f gets a std::integral_constant tag T (its value: T()), or
+// a value of the index type, and its result is returned.
+template <int V>
+using bn_int = std::integral_constant<int, V>;
+
+template <class F>   // an unknown activation is ACT_NONE
+static auto with_act(int act, F f) {
+  if (act == ACT_RELU) return f(bn_int<ACT_RELU>{});
+  if (act == ACT_TANH) return f(bn_int<ACT_TANH>{});
+  if (act == ACT_SIGMOID) return f(bn_int<ACT_SIGMOID>{});
+  return f(bn_int<ACT_NONE>{});
+}
+
+template <class F>   // relu / none at compile time; anything else the runtime-switch instance -1
+static auto with_act_rn(int act, F f) {
+  if (act == ACT_RELU) return f(bn_int<ACT_RELU>{});
+  if (act == ACT_NONE) return f(bn_int<ACT_NONE>{});
+  return f(bn_int<-1>{});
+}
+
+template <class F>   // channels per thread
+static auto with_vw(bool vec, F f) { return vec ? f(bn_int<8>{}) : f(bn_int<1>{}); }
+
+template <class F>   // index type: f(int{}) or f((long long){})
+static auto with_index(bool i32, F f) { return i32 ? f(int{}) : f((long long)0); }
+
+template <int... Vs, class F>   // v among Vs: f(tag); false, and no call, when v is none of them
+static bool with_int_of(int v, F f) { return ((v == Vs && (f(bn_int<Vs>{}), true)) || ...); }
+
+// the colstats_kernel instance of (vec, mode, act): mode 0 has no activation
+template <class F>
+static auto with_colstats(bool vec, int mode, int act, F f) {
+  return with_vw(vec, [&](auto VW) {
+    if (mode == 0) return f(VW, bn_int<0>{}, bn_int<ACT_NONE>{});
+    return with_act(act, [&](auto A) { return f(VW, bn_int<1>{}, A); });
+  });
 }
 
 // Workgroups for a colstats launch over M rows: one per 256 rows, capped at what the device
 // holds resident at once (the kernel walks its rows in a loop; a grid of 2048 over 768 resident
 // slots -- 134 VGPRs, 3 workgroups per CU -- spent its last third at 2/3 occupancy)
 extern "C" int fn_colstats_blocks(long long M, int C, int mode, int act) {
-  long long nb = M / 256;
-  if (nb < 1) nb = 1;
-  long long cap = 2048;
-  if (C % 8 == 0 && C / 8 <= 256) {
-    static int res[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
-    const int m = mode ? 1 : 0;
-    const int a = mode == 0 ? 0 : (act == ACT_RELU ? 1 : act == ACT_TANH ? 2 : act == ACT_SIGMOID ? 3 : 0);
-    if (res[m][a] < 0) {
-      const void* k = mode == 0 ? (const void*)colstats_kernel<8, 0, ACT_NONE>
-                    : a == 1 ? (const void*)colstats_kernel<8, 1, ACT_RELU>
-                    : a == 2 ? (const void*)colstats_kernel<8, 1, ACT_TANH>
-                    : a == 3 ? (const void*)colstats_kernel<8, 1, ACT_SIGMOID>
-                             : (const void*)colstats_kernel<8, 1, ACT_NONE>;
-      res[m][a] = bn_resident_blocks(k);
-    }
-    if (res[m][a] > 0) cap = res[m][a];
-  }
-  return (int)(nb > cap ? cap : nb);
+  int res = 0;
+  if (C % 8 == 0 && C / 8 <= 256)
+    res = with_colstats(true, mode, act, [](auto VW, auto MD, auto A) {
+      static const int r = bn_resident_blocks((const void*)colstats_kernel<VW(), MD(), A()>);
+      return r;
+    });
+  return resident_rows(M / 256, res);
 }
 
 extern "C" int fn_colstats(const void* x, const void* dz, const float* scale, const float* shift, const float* mean,
@@ -1183,21 +1203,10 @@ extern "C" int fn_colstats(const void* x, const void* dz, const float* scale, co
     }
   }
   const long long rpb = (M + nb - 1) / nb;
-  const bf16* xx = (const bf16*)x;
-  const bf16* dd = (const bf16*)dz;
-#define CS_CASE(VW, MD, A) \
-  hipLaunchKernelGGL((colstats_kernel<VW, MD, A>), dim3(nb), dim3(256), 0, st, xx, dd, scale, shift, mean, invstd, part, M, C, rpb)
-#define CS_ACT(VW)                                                                                  \
-  do {                                                                                              \
-    if (mode == 0) CS_CASE(VW, 0, ACT_NONE);                                                        \
-    else if (act == ACT_RELU) CS_CASE(VW, 1, ACT_RELU);                                             \
-    else if (act == ACT_TANH) CS_CASE(VW, 1, ACT_TANH);                                             \
-    else if (act == ACT_SIGMOID) CS_CASE(VW, 1, ACT_SIGMOID);                                       \
-    else CS_CASE(VW, 1, ACT_NONE);                                                                  \
-  } while (0)
-  if (vec) CS_ACT(8); else CS_ACT(1);
-#undef CS_ACT
-#undef CS_CASE
+  with_colstats(vec, mode, act, [&](auto VW, auto MD, auto A) {
+    hipLaunchKernelGGL((colstats_kernel<VW(), MD(), A()>), dim3(nb), dim3(256), 0, st, (const bf16*)x, (const bf16*)dz,
+                       scale, shift, mean, invstd, part, M, C, rpb);
+  });
   FN_CHECK_LAUNCH();
   return 0;
 }
@@ -1205,37 +1214,25 @@ extern "C" int fn_colstats(const void* x, const void* dz, const float* scale, co
 extern "C" int fn_bn_finalize(const float* part, int nb, int C, double count, const float* gamma, const float* beta,
                               float* run_mean, float* run_var, float momentum, float eps, float* o0, float* o1,
                               float* o2, float* o3, int mode, hipStream_t st) {
-  if (mode == 0)
-    hipLaunchKernelGGL(bn_finalize_kernel<0>, dim3(C), dim3(256), 0, st, part, nb, C, count, gamma, beta, run_mean,
+  if (mode == 2 && !(run_mean && run_var)) return -2;   // (mode 2 reads mean / invstd from them)
+  const bool known = with_int_of<0, 1, 2>(mode, [&](auto MD) {
+    hipLaunchKernelGGL(bn_finalize_kernel<MD()>, dim3(C), dim3(256), 0, st, part, nb, C, count, gamma, beta, run_mean,
                        run_var, momentum, eps, o0, o1, o2, o3);
-  else if (mode == 1)
-    hipLaunchKernelGGL(bn_finalize_kernel<1>, dim3(C), dim3(256), 0, st, part, nb, C, count, gamma, beta, run_mean,
-                       run_var, momentum, eps, o0, o1, o2, o3);
-  else if (mode == 2 && run_mean && run_var)
-    hipLaunchKernelGGL(bn_finalize_kernel<2>, dim3(C), dim3(256), 0, st, part, nb, C, count, gamma, beta, run_mean,
-                       run_var, momentum, eps, o0, o1, o2, o3);
-  else
-    return -2;
+  });
+  if (!known) return -2;
   FN_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int fn_bn_apply(const void* y, const float* scale, const float* shift, void* z, long long total, int C,
                            int act, hipStream_t st, void* mask) {
-  if (mask && (C % 8 || 256 % (C / 8))) return -2;   // (the fixed-chunk path writes the mask)
-#define BA_CASE(VW, A)                                                                                  \
-  hipLaunchKernelGGL((bn_apply_kernel<VW, A>), dim3(ew_blocks(total / VW)), dim3(256), 0, st, (const bf16*)y, scale, \
-                     shift, (bf16*)z, total, C, (unsigned char*)mask)
-#define BA_ACT(VW)                                                                                      \
-  do {                                                                                                  \
-    if (act == ACT_RELU) BA_CASE(VW, ACT_RELU);                                                         \
-    else if (act == ACT_TANH) BA_CASE(VW, ACT_TANH);                                                    \
-    else if (act == ACT_SIGMOID) BA_CASE(VW, ACT_SIGMOID);                                              \
-    else BA_CASE(VW, ACT_NONE);                                                                         \
-  } while (0)
-  if (C % 8 == 0) BA_ACT(8); else BA_ACT(1);
-#undef BA_ACT
-#undef BA_CASE
+  if (mask && !chunk_fixed(C)) return -2;        // (the fixed-chunk path writes the mask)
+  with_vw(C % 8 == 0, [&](auto VW) {
+    with_act(act, [&](auto A) {
+      hipLaunchKernelGGL((bn_apply_kernel<VW(), A()>), dim3(ew_blocks(total / VW())), dim3(256), 0, st, (const bf16*)y,
+                         scale, shift, (bf16*)z, total, C, (unsigned char*)mask);
+    });
+  });
   FN_CHECK_LAUNCH();
   return 0;
 }
@@ -1243,20 +1240,13 @@ extern "C" int fn_bn_apply(const void* y, const float* scale, const float* shift
 extern "C" int fn_bn_bwd_apply(const void* dz, const void* y, const float* scale, const float* shift,
                                const float* mean, const float* invstd, const float* dbeta, const float* dgamma,
                                void* dy, long long total, int C, float inv_count, int act, hipStream_t st) {
-#define BB_CASE(VW, A)                                                                                  \
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<VW, A>), dim3(ew_blocks(total / VW)), dim3(256), 0, st,            \
-                     (const bf16*)dz, (const bf16*)y, scale, shift, mean, invstd, dbeta, dgamma, (bf16*)dy, total, C, \
-                     inv_count)
-#define BB_ACT(VW)                                                                                      \
-  do {                                                                                                  \
-    if (act == ACT_RELU) BB_CASE(VW, ACT_RELU);                                                         \
-    else if (act == ACT_TANH) BB_CASE(VW, ACT_TANH);                                                    \
-    else if (act == ACT_SIGMOID) BB_CASE(VW, ACT_SIGMOID);                                              \
-    else BB_CASE(VW, ACT_NONE);                                                                         \
-  } while (0)
-  if (C % 8 == 0) BB_ACT(8); else BB_ACT(1);
-#undef BB_ACT
-#undef BB_CASE
+  with_vw(C % 8 == 0, [&](auto VW) {
+    with_act(act, [&](auto A) {
+      hipLaunchKernelGGL((bn_bwd_apply_kernel<VW(), A()>), dim3(ew_blocks(total / VW())), dim3(256), 0, st,
+                         (const bf16*)dz, (const bf16*)y, scale, shift, mean, invstd, dbeta, dgamma, (bf16*)dy, total,
+                         C, inv_count);
+    });
+  });
   FN_CHECK_LAUNCH();
   return 0;
 }
@@ -1265,43 +1255,35 @@ extern "C" int fn_bn_bwd_apply_s2d(const void* dz, const void* y, const float* s
                                    const float* mean, const float* invstd, const float* dbeta, const float* dgamma,
                                    void* dsh, int N, int FD, int FH, int FW, int C, float inv_count, int act,
                                    hipStream_t st) {
-  if (C % 8 || 256 % (C / 8) || FD % 2 || FH % 2 || FW % 2 || N < 1) return -2;
+  if (!chunk_fixed(C) || FD % 2 || FH % 2 || FW % 2 || N < 1) return -2;
   const long long nvec = (long long)N * (FD / 2 + 1) * (FH / 2 + 1) * (FW / 2 + 1) * 8 * (C / 8);
   const long long nrows = (long long)N * (FD / 2 + 1) * (FH / 2 + 1);
-  if ((act == ACT_RELU || act == ACT_NONE) && nrows < (1LL << 31) && nvec * 8 < (1LL << 40)) {
-    // the row form (grid-stride over the (n, cell-d, cell-h) rows)
+  if ((act == ACT_RELU || act == ACT_NONE) && C / 8 <= 32 && nrows < (1LL << 31) && nvec * 8 < (1LL << 40)) {
+    // the row form (grid-stride over the (n, cell-d, cell-h) rows): relu / none, up to 32 chunks
+    // (wider rows take the flat form below)
     int lc = 0;
     while ((1 << lc) < C / 8) ++lc;
     const unsigned grid = (unsigned)std::min<long long>(nrows, 8192);
     const long long rowlen = (long long)(FW / 2 + 1) * 8 * (C / 8);
     const int u = rowlen > 4 * 256 && rowlen <= 5 * 256 ? 5 : (rowlen > 5 * 256 && rowlen <= 8 * 256 ? 8 : 4);
-#define BR_CASE(A, L)                                                                                        \
-    if (lc == L) {                                                                                           \
-      if (u == 5) hipLaunchKernelGGL((bn_bwd_apply_s2d_rows_kernel<A, L, 5>), dim3(grid), dim3(256), 0, st,  \
-                                     (const bf16*)dz, (const bf16*)y, scale, shift, mean, invstd, dbeta, dgamma, \
-                                     (bf16*)dsh, N, FD, FH, FW, C, inv_count);                              \
-      else if (u == 8) hipLaunchKernelGGL((bn_bwd_apply_s2d_rows_kernel<A, L, 8>), dim3(grid), dim3(256), 0, \
-                                          st, (const bf16*)dz, (const bf16*)y, scale, shift, mean, invstd,  \
-                                          dbeta, dgamma, (bf16*)dsh, N, FD, FH, FW, C, inv_count);          \
-      else hipLaunchKernelGGL((bn_bwd_apply_s2d_rows_kernel<A, L, 4>), dim3(grid), dim3(256), 0, st,         \
-                              (const bf16*)dz, (const bf16*)y, scale, shift, mean, invstd, dbeta, dgamma,   \
-                              (bf16*)dsh, N, FD, FH, FW, C, inv_count);                                     \
-    }
-#define BR_ACT(A) BR_CASE(A, 0) BR_CASE(A, 1) BR_CASE(A, 2) BR_CASE(A, 3) BR_CASE(A, 4) BR_CASE(A, 5)
-    if (act == ACT_RELU) { BR_ACT(ACT_RELU) } else { BR_ACT(ACT_NONE) }
-#undef BR_ACT
-#undef BR_CASE
+    bool launched = false;
+    with_int_of<ACT_RELU, ACT_NONE>(act, [&](auto A) {
+      with_int_of<0, 1, 2, 3, 4, 5>(lc, [&](auto L) {
+        launched = with_int_of<4, 5, 8>(u, [&](auto U) {
+          hipLaunchKernelGGL((bn_bwd_apply_s2d_rows_kernel<A(), L(), U()>), dim3(grid), dim3(256), 0, st,
+                             (const bf16*)dz, (const bf16*)y, scale, shift, mean, invstd, dbeta, dgamma, (bf16*)dsh, N,
+                             FD, FH, FW, C, inv_count);
+        });
+      });
+    });
+    if (!launched) return -2;
     FN_CHECK_LAUNCH();
     return 0;
   }
-#define BS_CASE(A)                                                                                      \
-  hipLaunchKernelGGL((bn_bwd_apply_s2d_kernel<A>), dim3(ew_blocks(nvec)), dim3(256), 0, st, (const bf16*)dz, \
-                     (const bf16*)y, scale, shift, mean, invstd, dbeta, dgamma, (bf16*)dsh, N, FD, FH, FW, C, inv_count)
-  if (act == ACT_RELU) BS_CASE(ACT_RELU);
-  else if (act == ACT_TANH) BS_CASE(ACT_TANH);
-  else if (act == ACT_SIGMOID) BS_CASE(ACT_SIGMOID);
-  else BS_CASE(ACT_NONE);
-#undef BS_CASE
+  with_act(act, [&](auto A) {
+    hipLaunchKernelGGL((bn_bwd_apply_s2d_kernel<A()>), dim3(ew_blocks(nvec)), dim3(256), 0, st, (const bf16*)dz,
+                       (const bf16*)y, scale, shift, mean, invstd, dbeta, dgamma, (bf16*)dsh, N, FD, FH, FW, C, inv_count);
+  });
   FN_CHECK_LAUNCH();
   return 0;
 }
@@ -1322,29 +1304,21 @@ extern "C" int fn_pool_fwd(const void* x, void* out, const float* scale, const f
   const long long outs = (long long)g.N * g.OD * g.OH * g.OW;
   const bool win2 = g.KH == 2 && g.KW == 2 && (g.KD == 2 || g.KD == 1) && g.sd == g.KD && g.sh == 2 && g.sw == 2 &&
                     g.pd == 0 && g.ph == 0 && g.pw == 0 && g.D >= g.OD * g.KD && g.H >= g.OH * 2 &&
-                    g.W >= g.OW * 2 && g.C % 8 == 0 && 256 % (g.C / 8) == 0 &&
-                    outs * (g.C / 8) + 256LL * 8192 < (1LL << 31);
+                    g.W >= g.OW * 2 && chunk_fixed(g.C) && outs * (g.C / 8) + 256LL * 8192 < (1LL << 31);
   if (win2) {
     const int total = (int)(outs * (g.C / 8));
-    // (relu / none / no BN: compile-time instances; other activations the runtime one)
-    const int ka = !scale ? ACT_NONE : ((act == ACT_RELU || act == ACT_NONE) ? act : -1);
-#define P2_CASE(K, A)                                                                                         \
-    if (g.KD == K && ka == A) {                                                                               \
-      static const int res = bn_resident_blocks((const void*)pool2_fwd_kernel<K, A>);                         \
-      long long nbl = (total + 255) / 256;                                                                    \
-      if (res > 0 && nbl > res) nbl = res;                                                                    \
-      const unsigned nb = (unsigned)(nbl < 1 ? 1 : (nbl > 8192 ? 8192 : nbl));                                 \
-      hipLaunchKernelGGL((pool2_fwd_kernel<K, A>), dim3(nb), dim3(256), 0, st, (const bf16*)x, (bf16*)out,    \
-                         scale, shift, g, is_max, act, total);                                                \
-    }
-    P2_CASE(2, ACT_RELU) P2_CASE(2, ACT_NONE) P2_CASE(2, -1) P2_CASE(1, ACT_RELU) P2_CASE(1, ACT_NONE) P2_CASE(1, -1)
-#undef P2_CASE
-  } else if (g.C % 8 == 0)
-    hipLaunchKernelGGL(pool_fwd_kernel<8>, dim3(ew_blocks(outs * (g.C / 8))), dim3(256), 0, st, (const bf16*)x,
-                       (bf16*)out, scale, shift, g, is_max, count_pad, act);
-  else
-    hipLaunchKernelGGL(pool_fwd_kernel<1>, dim3(ew_blocks(outs * g.C)), dim3(256), 0, st, (const bf16*)x, (bf16*)out,
-                       scale, shift, g, is_max, count_pad, act);
+    with_int_of<2, 1>(g.KD, [&](auto K) {
+      with_act_rn(scale ? act : ACT_NONE, [&](auto A) {   // (no BN: the none instance)
+        static const int res = bn_resident_blocks((const void*)pool2_fwd_kernel<K(), A()>);
+        hipLaunchKernelGGL((pool2_fwd_kernel<K(), A()>), dim3(resident_grid((total + 255) / 256, res)), dim3(256), 0,
+                           st, (const bf16*)x, (bf16*)out, scale, shift, g, is_max, act, total);
+      });
+    });
+  } else
+    with_vw(g.C % 8 == 0, [&](auto VW) {
+      hipLaunchKernelGGL(pool_fwd_kernel<VW()>, dim3(ew_blocks(outs * (g.C / VW()))), dim3(256), 0, st, (const bf16*)x,
+                         (bf16*)out, scale, shift, g, is_max, count_pad, act);
+    });
   FN_CHECK_LAUNCH();
   return 0;
 }
@@ -1356,23 +1330,25 @@ static bool pool_i32(const PoolGeom& g) {
   return ins + 256LL * 8192 * 8 < (1LL << 31) && outs + 256LL * 8192 * 8 < (1LL << 31);
 }
 
-static bool pool_bwd_stats_ok(const PoolGeom& g) {
+// non-overlapping windows that tile the input: stride == kernel, no padding, dims divisible
+static bool pool_tiled(const PoolGeom& g) {
   return g.sd == g.KD && g.sh == g.KH && g.sw == g.KW && g.pd == 0 && g.ph == 0 && g.pw == 0 &&
-         g.D == g.OD * g.KD && g.H == g.OH * g.KH && g.W == g.OW * g.KW && g.C % 8 == 0 && 256 % (g.C / 8) == 0;
+         g.D == g.OD * g.KD && g.H == g.OH * g.KH && g.W == g.OW * g.KW;
 }
+
+static bool pool_bwd_stats_ok(const PoolGeom& g) { return pool_tiled(g) && chunk_fixed(g.C); }
 
 // blocks of the STATS launch (rows of its part slab); 0 when the geometry has no such path
 extern "C" int fn_pool_bwd_stats_blocks(const int* geom17) {
   const PoolGeom g = pool_geom(geom17);
   if (!pool_bwd_stats_ok(g)) return 0;
-  const long long w = ((long long)g.N * g.OD * g.OH * g.OW * (g.C / 8) + 255) / 256;
-  long long cap = 2048;
+  int res = 0;
   if (g.KD * g.KH * g.KW <= 8) {
     // the moments kernel's grid-stride loop: one resident wave of workgroups (no tail round)
-    static const int res = bn_resident_blocks((const void*)pool_bn_moments8_kernel<int>);
-    if (res > 0) cap = res;
+    static const int r = bn_resident_blocks((const void*)pool_bn_moments8_kernel<int>);
+    res = r;
   }
-  return (int)(w < 1 ? 1 : (w > cap ? cap : w));
+  return resident_rows(((long long)g.N * g.OD * g.OH * g.OW * (g.C / 8) + 255) / 256, res);
 }
 
 // max-pool backward of a BN+act output plus that BN's raw backward moments (see
@@ -1383,15 +1359,12 @@ extern "C" int fn_pool_bwd_stats(const void* dout, const void* x, void* dx, cons
   const int nb = fn_pool_bwd_stats_blocks(geom17);
   if (nb <= 0 || !scale || !shift || !part) return -2;
   if (!dx && g.KD * g.KH * g.KW <= 8) {          // moments only: the bandwidth form
-    const bool i32 = pool_i32(g);
-    const int ka = (act == ACT_RELU || act == ACT_NONE) ? act : -1;
-#define PM_CASE(I, A)                                                                                          \
-    if (i32 == std::is_same<I, int>::value && ka == A)                                                         \
-      hipLaunchKernelGGL((pool_bn_moments8_kernel<I, A>), dim3(nb), dim3(256), 0, st, (const bf16*)dout,        \
-                         (const bf16*)x, scale, shift, g, act, part);
-    PM_CASE(int, ACT_RELU) PM_CASE(int, ACT_NONE) PM_CASE(int, -1)
-    PM_CASE(long long, ACT_RELU) PM_CASE(long long, ACT_NONE) PM_CASE(long long, -1)
-#undef PM_CASE
+    with_index(pool_i32(g), [&](auto I) {
+      with_act_rn(act, [&](auto A) {
+        hipLaunchKernelGGL((pool_bn_moments8_kernel<decltype(I), A()>), dim3(nb), dim3(256), 0, st, (const bf16*)dout,
+                           (const bf16*)x, scale, shift, g, act, part);
+      });
+    });
   } else
     hipLaunchKernelGGL((pool_bwd_tiled_kernel<8, true>), dim3(nb), dim3(256), 0, st, (const bf16*)dout, (const bf16*)x,
                        (bf16*)dx, scale, shift, g, 1, act, part);
@@ -1405,23 +1378,16 @@ extern "C" int fn_pool_bn_bwd_apply(const void* dout, const void* y, const float
                                     const float* mean, const float* invstd, const float* dbeta, const float* dgamma,
                                     void* dy, const int* geom17, int act, float inv_count, hipStream_t st) {
   const PoolGeom g = pool_geom(geom17);
-  const bool tiled = g.sd == g.KD && g.sh == g.KH && g.sw == g.KW && g.pd == 0 && g.ph == 0 && g.pw == 0 &&
-                     g.D == g.OD * g.KD && g.H == g.OH * g.KH && g.W == g.OW * g.KW;
-  if (!tiled || g.C % 8 || 256 % (g.C / 8) || g.KD * g.KH * g.KW > 8) return -2;
+  if (!pool_tiled(g) || !chunk_fixed(g.C) || g.KD * g.KH * g.KW > 8) return -2;
   const long long outs = (long long)g.N * g.OD * g.OH * g.OW;
   static const int res = bn_resident_blocks((const void*)pool_bn_bwd_apply_kernel<int>);
-  long long nbl = (outs * (g.C / 8) + 255) / 256;
-  if (res > 0 && nbl > res) nbl = res;           // one resident wave of workgroups, grid-stride
-  const unsigned nb = (unsigned)(nbl < 1 ? 1 : (nbl > 8192 ? 8192 : nbl));
-  const bool i32 = pool_i32(g);
-  const int ka = (act == ACT_RELU || act == ACT_NONE) ? act : -1;
-#define PA_CASE(I, A)                                                                                           \
-  if (i32 == std::is_same<I, int>::value && ka == A)                                                            \
-    hipLaunchKernelGGL((pool_bn_bwd_apply_kernel<I, A>), dim3(nb), dim3(256), 0, st, (const bf16*)dout,          \
-                       (const bf16*)y, scale, shift, mean, invstd, dbeta, dgamma, (bf16*)dy, g, act, inv_count);
-  PA_CASE(int, ACT_RELU) PA_CASE(int, ACT_NONE) PA_CASE(int, -1)
-  PA_CASE(long long, ACT_RELU) PA_CASE(long long, ACT_NONE) PA_CASE(long long, -1)
-#undef PA_CASE
+  const unsigned nb = resident_grid((outs * (g.C / 8) + 255) / 256, res);   // grid-stride
+  with_index(pool_i32(g), [&](auto I) {
+    with_act_rn(act, [&](auto A) {
+      hipLaunchKernelGGL((pool_bn_bwd_apply_kernel<decltype(I), A()>), dim3(nb), dim3(256), 0, st, (const bf16*)dout,
+                         (const bf16*)y, scale, shift, mean, invstd, dbeta, dgamma, (bf16*)dy, g, act, inv_count);
+    });
+  });
   FN_CHECK_LAUNCH();
   return 0;
 }
@@ -1429,29 +1395,21 @@ extern "C" int fn_pool_bn_bwd_apply(const void* dout, const void* y, const float
 extern "C" int fn_pool_bwd(const void* dout, const void* x, void* dx, const float* scale, const float* shift,
                            const int* geom17, int is_max, int count_pad, int act, hipStream_t st) {
   PoolGeom g = pool_geom(geom17);
-  const long long ins = (long long)g.N * g.D * g.H * g.W;
-  const bool tiled = g.sd == g.KD && g.sh == g.KH && g.sw == g.KW && g.pd == 0 && g.ph == 0 && g.pw == 0 &&
-                     g.D == g.OD * g.KD && g.H == g.OH * g.KH && g.W == g.OW * g.KW;
-  if (tiled) {
+  if (pool_tiled(g)) {
     const long long outs = (long long)g.N * g.OD * g.OH * g.OW;
-    if (g.C % 8 == 0)
-      hipLaunchKernelGGL(pool_bwd_tiled_kernel<8>, dim3(ew_blocks(outs * (g.C / 8))), dim3(256), 0, st,
+    with_vw(g.C % 8 == 0, [&](auto VW) {
+      hipLaunchKernelGGL(pool_bwd_tiled_kernel<VW()>, dim3(ew_blocks(outs * (g.C / VW()))), dim3(256), 0, st,
                          (const bf16*)dout, (const bf16*)x, (bf16*)dx, scale, shift, g, is_max, act);
-    else
-      hipLaunchKernelGGL(pool_bwd_tiled_kernel<1>, dim3(ew_blocks(outs * g.C)), dim3(256), 0, st, (const bf16*)dout,
-                         (const bf16*)x, (bf16*)dx, scale, shift, g, is_max, act);
+    });
     FN_CHECK_LAUNCH();
     return 0;
   }
-  if (g.C % 8 == 0)
-    hipLaunchKernelGGL(pool_bwd_kernel<8>, dim3(ew_blocks(ins * (g.C / 8))), dim3(256), 0, st, (const bf16*)dout,
+  const long long ins = (long long)g.N * g.D * g.H * g.W;
+  // (channel pairs: the window walk once per two, e.g. LeNet's 18)
+  with_int_of<8, 2, 1>(g.C % 8 == 0 ? 8 : (g.C % 2 == 0 ? 2 : 1), [&](auto VW) {
+    hipLaunchKernelGGL(pool_bwd_kernel<VW()>, dim3(ew_blocks(ins * (g.C / VW()))), dim3(256), 0, st, (const bf16*)dout,
                        (const bf16*)x, (bf16*)dx, scale, shift, g, is_max, count_pad, act);
-  else if (g.C % 2 == 0)                         // (channel pairs: the window walk once per two, e.g.
-    hipLaunchKernelGGL(pool_bwd_kernel<2>, dim3(ew_blocks(ins * (g.C / 2))), dim3(256), 0, st,   // LeNet's 18)
-                       (const bf16*)dout, (const bf16*)x, (bf16*)dx, scale, shift, g, is_max, count_pad, act);
-  else
-    hipLaunchKernelGGL(pool_bwd_kernel<1>, dim3(ew_blocks(ins * g.C)), dim3(256), 0, st, (const bf16*)dout,
-                       (const bf16*)x, (bf16*)dx, scale, shift, g, is_max, count_pad, act);
+  });
   FN_CHECK_LAUNCH();
   return 0;
 }
@@ -1478,16 +1436,13 @@ extern "C" int fn_bn_bwd_prep(const float* gslab, int nbg, const float* wpart, i
 // workgroups of bn_bwd_apply_k (its partial-sum rows): one resident wave of them
 extern "C" int fn_bn_bwd_apply_k_blocks(long long M, int C) {
   static const int res = bn_resident_blocks((const void*)bn_bwd_apply_k_kernel);
-  long long nb = (M * (C / 8) + 255) / 256;
-  const long long cap = res > 0 ? res : 2048;
-  if (nb > cap) nb = cap;
-  return (int)(nb < 1 ? 1 : nb);
+  return resident_rows((M * (C / 8) + 255) / 256, res);
 }
 
 extern "C" int fn_bn_bwd_apply_k(const void* g, const void* y, const float* kc, const float* mean,
                                  const float* invstd, const float* shift, void* dy, long long M, int C, float* part,
                                  int nb, hipStream_t st) {
-  if (C % 8 || 256 % (C / 8) || nb < 1) return -2;
+  if (!chunk_fixed(C) || nb < 1) return -2;
   hipLaunchKernelGGL(bn_bwd_apply_k_kernel, dim3(nb), dim3(256), 0, st, (const bf16*)g, (const bf16*)y, kc, mean,
                      invstd, shift, (bf16*)dy, M * (C / 8), C, part);
   FN_CHECK_LAUNCH();
