@@ -9,7 +9,7 @@ Two shared objects are produced next to this file:
   data pipeline (``csrc/runtime``).
 
 Object files are cached under ``build/obj`` and rebuilt when a source or any
-header in its directory is newer than the object.  ``python -m
+header in its directory or in ``csrc/shared`` is newer than the object.  ``python -m
 featurenet_amd._build`` builds everything; ``__graft_entry__.build()`` calls
 :func:`build_all`.
 """
@@ -40,7 +40,8 @@ def _newer(src: Path, obj: Path) -> bool:
     if not obj.exists():
         return True
     t = obj.stat().st_mtime
-    deps = [src] + [p for p in src.parent.glob("*.h")]
+    # csrc/shared: headers that both libraries include (the part predicates of partgen.h)
+    deps = [src] + [p for p in src.parent.glob("*.h")] + [p for p in (PKG / "csrc" / "shared").glob("*.h")]
     return any(d.stat().st_mtime > t for d in deps)
 
 

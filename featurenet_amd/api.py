@@ -1,6 +1,6 @@
 """Public Python API: ``train()``, ``classify()``, ``segment()``, ``extract_features()``,
 ``label_components()``, ``evaluate()``, ``evaluate_segmentation()``, ``evaluate_features()``,
-``match_features()``, ``load()``, ``save()``, ``build_model()`` and ``search()``.
+``match_features()``, ``generate_parts()``, ``load()``, ``save()``, ``build_model()`` and ``search()``.
 
 Reference parity: the de-facto entry point of the reference is the
 ``TensorflowGenerator(product, epochs, dataset, ...)`` constructor
@@ -11,6 +11,7 @@ pipeline is split into composable calls:
     >>> import featurenet_amd as fn
     >>> res = fn.train("featurenet3d", data="voxel", epochs=2)        # 64^3, 24 classes
     >>> labels, probs = fn.classify(res.path, voxels)
+    >>> seg = fn.train("segmentation", data="voxel-seg", epochs=4)     # per-voxel labels, generated parts
     >>> res = fn.train("lenet5", data="mnist", epochs=12)              # NAS template
     >>> res = fn.train(product_tree, data="cifar", epochs=25)          # a PLEDGE product
 
@@ -430,6 +431,33 @@ def match_features(pred_labels, true_labels, background: int | None = 0, connect
     five = overlap.instance_overlap(pt.to(device).to(torch.uint8), tt.to(device).to(torch.uint8), background,
                                     connectivity)
     return FeatureScore.from_tables(*five, iou_threshold=iou_threshold, min_voxels=min_voxels)
+
+
+def generate_parts(n: int, size: int = 64, seed: int = 0, features=(1, 4), separate: bool = True, device=None,
+                   return_slots: bool = False):
+    """``n`` procedural machining parts with per-voxel truth -> ``(voxels, labels, parts)`` or
+    ``(voxels, labels, parts, slots)``.
+
+    A part is a solid ``size``^3 stock block with ``features = (lo, hi)`` subtractive features of
+    the 24 classes, each entering from one of the six faces.  ``voxels`` uint8 ``[n, S, S, S]`` is
+    the occupancy, ``labels`` uint8 ``[n, S, S, S]`` is 0 where nothing was removed and 1 + class
+    where a feature of that class removed the voxel, ``parts`` holds one list of
+    :class:`~featurenet_amd.utils.partfeatures.PartFeature` per part, and ``slots`` (uint8) names
+    the removing feature as 1 + its ``slot``.  With ``separate`` the features' bounding boxes keep
+    a voxel apart, so every feature is its own connected component of ``labels``; without it
+    features may overlap and the one in the lowest slot owns the shared voxels.  Deterministic per
+    ``(seed, part index)`` and the same on every device: ``device`` (default: the GPU when there
+    is one) only chooses between the ``partgen_carve`` kernel and the host path.
+    """
+    from .ops import partgen
+    from .utils.partfeatures import from_params
+
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    tab = partgen.sample(n, size, seed, features, separate=separate)
+    out = partgen.carve(tab, size, device=device, want_slots=return_slots)
+    arrays = [t.cpu().numpy() for t in out]
+    return (arrays[0], arrays[1], from_params(tab), *arrays[2:])
 
 
 def evaluate(model, x, y, batch_size: int = 256, packed_size: int | None = None) -> float:

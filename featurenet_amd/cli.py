@@ -18,6 +18,8 @@ score      confusion matrix / per-class IoU / mIoU of a segmentation checkpoint 
 features   the feature instances (connected components of the labels) of a segmentation checkpoint -> JSON
 score-features
            predicted features matched to the true ones: per-class TP / FP / FN, F1 and panoptic quality
+generate-parts
+           procedural multi-feature parts with per-voxel labels (and their feature lists) -> .npz
 extend     ``PledgeEvolution.end2end`` (FM template -> B x C)
 sample     ``run_pledge`` (native diverse product sampler)
 template   write the built-in 1-block search-space FM
@@ -272,6 +274,23 @@ def cmd_score_features(a) -> int:
     return 0
 
 
+def cmd_generate_parts(a) -> int:
+    import numpy as np
+
+    from . import api
+
+    voxels, labels, parts = api.generate_parts(a.n, size=a.size, seed=a.seed, features=tuple(a.features),
+                                               separate=not a.overlap, device=a.device or None)
+    np.savez_compressed(a.output, voxels=voxels, labels=labels)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(json.dumps({"parts": [[p.to_dict() for p in ps] for ps in parts]}) + "\n")
+    counts = np.bincount([len(ps) for ps in parts], minlength=a.features[1] + 1)
+    print(json.dumps({"shape": list(labels.shape), "features_per_part": counts.tolist(),
+                      "removed_voxels": int((labels != 0).sum())}))
+    return 0
+
+
 def cmd_extend(a) -> int:
     from .fm.extend import generate_featuretree
 
@@ -451,6 +470,18 @@ def build_parser() -> argparse.ArgumentParser:
                     help="class that forms no instance (default 0; -1: every class does)")
     sf.add_argument("--packed-size", type=int, default=None)
     sf.set_defaults(fn=cmd_score_features)
+
+    gp = sub.add_parser("generate-parts", help="procedural multi-feature parts with per-voxel labels -> .npz")
+    gp.add_argument("-n", type=int, default=16, help="number of parts")
+    gp.add_argument("--size", type=int, default=64, help="grid edge (a multiple of 8, at most 256)")
+    gp.add_argument("--seed", type=int, default=0)
+    gp.add_argument("--features", type=int, nargs=2, default=[1, 4], metavar=("LO", "HI"),
+                    help="features per part")
+    gp.add_argument("--overlap", action="store_true", help="let features overlap (the lowest slot owns shared voxels)")
+    gp.add_argument("--device", default="", help="cuda / cpu (default: the GPU when there is one)")
+    gp.add_argument("-o", "--output", required=True, help="voxels and labels, uint8 [N, S, S, S] each (.npz)")
+    gp.add_argument("--json", default="", metavar="OUT", help="also write the per-part feature lists to this file")
+    gp.set_defaults(fn=cmd_generate_parts)
 
     e = sub.add_parser("extend", help="expand the 1-block template to B x C")
     e.add_argument("--input", default="")

@@ -45,6 +45,8 @@ int fn_ccl_local(const void*, void*, int, int, int, int, int, int, hipStream_t);
 int fn_ccl_merge(const void*, void*, int, int, int, int, int, int, hipStream_t);
 int fn_ccl_flatten(void*, void*, int, int, int, int, hipStream_t);
 int fn_ccl_stats(const void*, const void*, const void*, void*, void*, int, int, int, int, long long, hipStream_t);
+int fn_partgen_chunk();
+int fn_partgen_carve(const void*, void*, void*, void*, void*, int, int, int, hipStream_t);
 void fn_overlap_chunk(int*);
 int fn_overlap_pairs(const void*, const void*, const void*, const void*, void*, void*, void*, int, long long, int,
                      long long, long long, hipStream_t);
@@ -737,6 +739,23 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("ids_a"), py::arg("ids_b"), py::arg("off_a"), py::arg("off_b"), py::arg("keys"), py::arg("counts"),
      py::arg("lost"), py::arg("N"), py::arg("V"), py::arg("W"), py::arg("cap"), py::arg("probe"), py::arg("st"),
      py::arg("ext"));
+  // multi-feature parts from their parameter tables (partgen.hip): params int32 [N][K][16]; occ / labels / slots
+  // uint8 [N][S][S][S] (8-byte aligned) and packed uint8 [N][S^3/8], each 0 = not wanted; S % 8 == 0, 8 <= S <=
+  // 256, K <= 32; ext = {numel(params), numel(occ), numel(packed), numel(labels), numel(slots)}
+  m.def("partgen_chunk", []() { return fn_partgen_chunk(); });
+  m.def("partgen_carve", [](uintptr_t params, uintptr_t occ, uintptr_t packed, uintptr_t labels, uintptr_t slots,
+                            int N, int K, int size, uintptr_t st, std::vector<long long> ext) {
+    const long long vox = prod({N, size, size, size});
+    fits(ext, 0, prod({N, K, 16}), "partgen_carve", "params");
+    if (occ) fits(ext, 1, vox, "partgen_carve", "occ");
+    if (packed) fits(ext, 2, vox < 0 ? -1 : vox / 8, "partgen_carve", "packed");
+    if (labels) fits(ext, 3, vox, "partgen_carve", "labels");
+    if (slots) fits(ext, 4, vox, "partgen_carve", "slots");
+    chk(fn_partgen_carve(P<const void*>(params), P<void*>(occ), P<void*>(packed), P<void*>(labels), P<void*>(slots),
+                         N, K, size, S(st)),
+        "partgen_carve");
+  }, py::arg("params"), py::arg("occ"), py::arg("packed"), py::arg("labels"), py::arg("slots"), py::arg("N"),
+     py::arg("K"), py::arg("S"), py::arg("st"), py::arg("ext"));
   // part: fp32 scratch of pw_wgrad_blocks(M, K, N) x N x K floats (per-workgroup partials)
   m.def("pw_wgrad", [](uintptr_t dy, uintptr_t x, uintptr_t dw, long long M, int K, int N, uintptr_t st,
                        uintptr_t psc, uintptr_t psh, int pact, uintptr_t part, long long part_n) {

@@ -248,3 +248,115 @@ def overlap_table(ids_a: torch.Tensor, off_a: torch.Tensor, ids_b: torch.Tensor,
     rb = b + off_b.to(torch.int64)[:-1, None] - 1
     keys, counts = torch.unique((ra << 32 | rb)[both], return_counts=True)
     return torch.stack([keys >> 32, keys & 0xffffffff, counts], 1)
+
+
+def _part_volume(cls: int, f: dict, X, Y, Z, top: int):
+    """The volume of one feature class over canonical quarter-voxel coordinates ``X, Y, Z``
+    (int64 ``[n, S, S, S]``); ``f`` maps the field names of a table row to ``[n, 1, 1, 1]``."""
+    u, v, dz = X - f["cu"], Y - f["cv"], top - Z
+    r, a, b, depth, w = f["r"], f["a"], f["b"], f["depth"], f["w"]
+
+    def circle(p, q, rad):
+        return p * p + q * q <= rad * rad
+
+    def rect(p, q, ha, hb):
+        return (p.abs() <= ha) & (q.abs() <= hb)
+
+    def tri(p, q, rad):
+        return (2 * q >= -rad) & (q <= rad) & (3 * p * p <= (rad - q) ** 2)
+
+    def hexagon(p, q, rad):
+        return (4 * q * q <= 3 * rad * rad) & (p.abs() <= rad) & (q * q <= 3 * (rad - p.abs()) ** 2)
+
+    def slot_ends(p, q):
+        return rect(p, q, a, r) | circle(p - a, q, r) | circle(p + a, q, r)
+
+    blind = dz <= depth
+    if cls == 0:
+        return blind & circle(u, v, r) & ~circle(u, v, f["r2"])
+    if cls in (1, 2):
+        return blind & circle(u, v, r)
+    if cls in (3, 9):
+        return blind & tri(u, v, r)
+    if cls in (4, 10):
+        return blind & rect(u, v, a, b)
+    if cls in (5, 11):
+        return blind & slot_ends(u, v)
+    if cls == 6:
+        return blind & (5 * u.abs() <= 3 * (depth - dz))
+    if cls == 7:
+        return blind & (u.abs() <= a)
+    if cls == 8:
+        return blind & (u.abs() <= a) & (v <= b)
+    if cls == 12:
+        return blind & (X + Y <= r)
+    if cls == 13:
+        return blind & circle(X, Y, r)
+    if cls == 14:
+        return blind & (X <= a) & (Y <= b)
+    if cls == 15:
+        return blind & (X <= a)
+    if cls == 16:
+        return blind & ((X <= a) | (X >= top - a))
+    if cls == 17:
+        return blind & (2 * X * depth <= 4 * a * (depth - dz) + a * depth)
+    if cls == 18:
+        return X + dz < w
+    if cls == 19:
+        return (X < w) & (dz < w) & ((w - X) ** 2 + (w - dz) ** 2 > w * w)
+    if cls == 20:
+        return blind & (((u.abs() <= r) & (v <= 0)) | circle(u, v, r))
+    if cls == 21:
+        return (v <= b) & (((dz <= depth - r) & (u.abs() <= r)) | circle(u, dz - (depth - r), r))
+    if cls in (22, 23):
+        return blind & hexagon(u, v, r)
+    raise ValueError(f"carve_parts: class {cls} outside -1..23")
+
+
+PART_FIELDS = ("cls", "orient", "cu", "cv", "r", "r2", "a", "b", "depth", "w", "x0", "x1", "y0", "y1", "z0", "z1")
+
+
+def carve_parts(params: torch.Tensor, size: int):
+    """Multi-feature parts from their parameter tables -> ``(occupancy, labels, slots)``, each
+    uint8 ``[N, S, S, S]`` on the table's device.
+
+    ``params`` int32 ``[N, K, 16]``, a row being ``cls, orient, cu, cv, r, r2, a, b, depth, w`` and
+    the feature's bounding box ``x0, x1, y0, y1, z0, z1`` (which this function does not read: a
+    box is never smaller than its feature).  ``cls`` -1 is an unused slot.  ``orient = o + 6 fx +
+    12 fy``: output voxel ``(X, Y, Z)`` is canonical voxel ``(x, y, z)`` mirrored in x (``fx``)
+    and y (``fy``) and then turned so that the canonical top face z = S-1 becomes face ``o`` (+z,
+    -z, +x, -x, +y, -y).  Geometry is in quarter voxels, voxel centres at multiples of 4.
+    ``labels`` is 1 + the class of the lowest slot whose volume holds the voxel, ``slots`` 1 + that
+    slot, both 0 where there is none, and ``occupancy`` is 1 exactly there.  Exact integers
+    (int64 throughout): the oracle of ``partgen_carve`` and ``_rt.carve_parts``."""
+    if params.dim() != 3 or params.shape[2] != 16 or params.dtype != torch.int32:
+        raise ValueError(f"carve_parts: params must be int32 [N, K, 16], not {params.dtype} {tuple(params.shape)}")
+    N, K, _ = params.shape
+    S, dev = int(size), params.device
+    e, top = S - 1, 4 * (S - 1)
+    p = params.to(torch.int64)
+    ax = torch.arange(S, device=dev, dtype=torch.int64)
+    Zo, Yo, Xo = (t.expand(1, S, S, S) for t in torch.meshgrid(ax, ax, ax, indexing="ij"))
+    labels = torch.zeros(N, S, S, S, dtype=torch.uint8, device=dev)
+    slots = torch.zeros_like(labels)
+    # canonical (x, y, z) of an output voxel for each access face, before the mirrors
+    faces = [(Xo, Yo, Zo), (Xo, e - Yo, e - Zo), (e - Zo, Yo, Xo), (Zo, Yo, e - Xo), (Xo, e - Zo, Yo),
+             (Xo, Zo, e - Yo)]
+    for k in reversed(range(K)):                 # the lowest slot is painted last: it wins
+        for cls in p[:, k, 0].unique().tolist():
+            if cls == -1:
+                continue
+            for orient in p[p[:, k, 0] == cls, k, 1].unique().tolist():
+                if not 0 <= orient < 24:
+                    raise ValueError(f"carve_parts: orient {orient} outside 0..23")
+                sel = ((p[:, k, 0] == cls) & (p[:, k, 1] == orient)).nonzero().squeeze(1)
+                x, y, z = faces[orient % 6]
+                if orient // 6 % 2:
+                    x = e - x
+                if orient // 12:
+                    y = e - y
+                f = {name: p[sel, k, i].view(-1, 1, 1, 1) for i, name in enumerate(PART_FIELDS)}
+                vol = _part_volume(int(cls), f, 4 * x, 4 * y, 4 * z, top)
+                labels[sel] = torch.where(vol, torch.full_like(labels[sel], cls + 1), labels[sel])
+                slots[sel] = torch.where(vol, torch.full_like(slots[sel], k + 1), slots[sel])
+    return (labels == 0).to(torch.uint8), labels, slots

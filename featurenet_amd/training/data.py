@@ -12,7 +12,9 @@ present (``$FEATURENET_DATA`` or ``~/.keras/datasets``: ``mnist.npz``,
 unpickling) and otherwise replaced by a synthetic stand-in of identical
 shape and class count (``Dataset.synthetic`` is then True and every report
 says so).  The voxel workload uses the native procedural generator
-(``csrc/runtime/voxel.cpp``) or a folder of ``.binvox`` files.
+(``csrc/runtime/voxel.cpp``) or a folder of ``.binvox`` files; the segmentation workload
+(``voxel-seg``) uses multi-feature parts with per-voxel labels, carved on the device
+(``ops.partgen``).
 
 Everything is kept on the GPU (a full CIFAR epoch is ~150 MB; HBM is
 288 GB), shuffling is a device permutation and augmentation runs as batched
@@ -31,7 +33,8 @@ import torch
 
 from .. import _native
 
-DATASET_CLASSES = {"mnist": 10, "cifar": 10, "cifar10": 10, "cifar100": 100, "voxel": 24, "featurenet24": 24}
+DATASET_CLASSES = {"mnist": 10, "cifar": 10, "cifar10": 10, "cifar100": 100, "voxel": 24, "featurenet24": 24,
+                   "voxel-seg": 25}
 DATASET_SHAPES = {"mnist": (28, 28, 1), "cifar": (32, 32, 3), "cifar10": (32, 32, 3), "cifar100": (32, 32, 3)}
 
 
@@ -129,13 +132,16 @@ def _synthetic_images(shape, n_classes, n_train, n_test, seed):
 
 
 def load_dataset(name: str, synthetic_sizes=(6000, 1000), seed: int = 0, allow_synthetic: bool = True) -> Dataset:
-    """``mnist`` / ``cifar`` (= ``cifar10``) / ``cifar100`` / ``voxel``; cached per name."""
+    """``mnist`` / ``cifar`` (= ``cifar10``) / ``cifar100`` / ``voxel`` / ``voxel-seg``; cached per name."""
     key = (name, synthetic_sizes, seed)
     if key in _CACHE:
         return _CACHE[key]
     name_l = name.lower()
     if name_l in ("voxel", "featurenet24"):
         ds = voxel_dataset(*synthetic_sizes, size=64, seed=seed)
+    elif name_l in ("voxel-seg", "voxel_seg"):
+        # 64^3 label volumes: a tenth of the classification set's sample count (0.5 MB per part)
+        ds = voxel_seg_dataset(max(1, synthetic_sizes[0] // 10), max(1, synthetic_sizes[1] // 10), size=64, seed=seed)
     else:
         loader = {"mnist": _load_mnist, "cifar": _load_cifar10, "cifar10": _load_cifar10,
                   "cifar100": _load_cifar100}.get(name_l)
@@ -166,6 +172,29 @@ def voxel_dataset(n_train: int, n_test: int, size: int = 64, num_classes: int = 
     xte, yte = rt.generate_voxels(n_test, size, seed + 1_000_003, num_classes)
     return Dataset("voxel", xtr, ytr, xte, yte, num_classes, (size, size, size, 1), synthetic=True, packed=True,
                    meta={"generator": "featurenet_amd._rt.generate_voxels", "seed": seed})
+
+
+def voxel_seg_dataset(n_train: int, n_test: int, size: int = 64, features=(1, 4), seed: int = 0,
+                      device=None) -> Dataset:
+    """Procedural multi-feature parts with per-voxel truth (``ops.partgen``): ``x`` uint8
+    ``[N, S, S, S, 1]`` occupancy, ``y`` uint8 ``[N, S, S, S]`` (0 = material or air the stock
+    never filled, 1 + class = removed by a feature of that class), 25 classes.  Carved on the GPU
+    when there is one (``device`` None) and kept there; ``meta["params_train"]`` /
+    ``meta["params_test"]`` are the parameter tables (CPU), the feature lists of every part."""
+    from ..ops import partgen
+
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    parts, tables = [], []
+    for n, sd in ((n_train, seed), (n_test, seed + 1_000_003)):
+        tab = partgen.sample(n, size, sd, features)
+        vox, lab = partgen.carve(tab, size, device=device)
+        parts += [vox.unsqueeze(-1), lab]
+        tables.append(tab)
+    return Dataset("voxel-seg", parts[0], parts[1], parts[2], parts[3], partgen.NUM_CLASSES + 1,
+                   (size, size, size, 1), synthetic=True,
+                   meta={"generator": "featurenet_amd._rt.sample_parts", "seed": seed, "features": tuple(features),
+                         "params_train": tables[0], "params_test": tables[1]})
 
 
 def binvox_folder(root: str | Path, size: int | None = None) -> tuple[np.ndarray, np.ndarray, list[str]]:
