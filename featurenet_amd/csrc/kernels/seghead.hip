@@ -241,7 +241,11 @@ __global__ __launch_bounds__(SH_NTHR, 2) void seghead_loss_kernel(const bf16* __
         }
         const float se = sp.x + sp.y;
         const float lse = mx + __logf(se), inv = 1.f / se;
-        const float lrow = XF ? lse - (off * vs + (yin ? (on - off) * vy : 0.f)) : lse - (yin ? vy : 0.f);
+        // (a label outside [0, NC) has no target class: every class gets `off`, as in
+        // softmax_xent_tile_kernel and the XENT epilogue of pw_fwd_kernel -- the row's loss is
+        // smoothing * lse - off * sum_c v_c, 0 in the lean instance, and the row is never a hit)
+        const float lrow = XF ? (yin ? lse : smoothing * lse) - (off * vs + (yin ? (on - off) * vy : 0.f))
+                              : (yin ? lse - vy : 0.f);
         // d = (softmax - off) * xscale = e * (inv xscale) - off xscale, pairs on v_pk_fma_f32
         const ct_f32x2 ix = {inv * xscale, inv * xscale}, ox = {-off * xscale, -off * xscale};
 #pragma unroll
@@ -260,7 +264,7 @@ __global__ __launch_bounds__(SH_NTHR, 2) void seghead_loss_kernel(const bf16* __
         if (yin)                                 // the target's d
           orow[ylab] = f2bf(__builtin_amdgcn_exp2f(__builtin_fmaf(vy, L2E, nml.x)) * ix.x - on * xscale);
         xl += lrow;
-        if constexpr (XF) xc += (am == ylab) ? 1.f : 0.f;
+        if constexpr (XF) xc += (yin && am == ylab) ? 1.f : 0.f;
       } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) *(uint4*)(orow + 8 * j) = make_uint4(0u, 0u, 0u, 0u);
@@ -404,7 +408,8 @@ extern "C" int fn_seghead_blocks(long long M) {
 // y [M][32] bf16 (M % 8 == 0), sc / sh [32], w [NC][32] bf16 (NC <= 32), bias [NC] or null,
 // labels int64 [M] (lab8 = 0) or uint8 [M] (lab8 = 1), dz [M][32] bf16, part fp32
 // [fn_seghead_blocks(M)][fn_seghead_part_len()]; hits = 0: the caller does not read part's hits
-// column (0 there with smoothing == 0 and 25 classes)
+// column (0 there with smoothing == 0 and 25 classes).  A label outside [0, NC) has no target class
+// (every class gets smoothing / NC) and is never a hit, as in the other loss kernels.
 extern "C" int fn_seghead_loss(const void* y, const float* sc, const float* sh, const void* w, const float* bias,
                                const void* labels, void* dz, float* part, long long M, int K, int NC, int act,
                                float xscale, float smoothing, hipStream_t st, int lab8, int hits) {
