@@ -460,6 +460,73 @@ def generate_parts(n: int, size: int = 64, seed: int = 0, features=(1, 4), separ
     return (arrays[0], arrays[1], from_params(tab), *arrays[2:])
 
 
+def _mesh_triangles(mesh) -> np.ndarray:
+    """One mesh of :func:`voxelize` -> float64 ``[F, 3, 3]``."""
+    if isinstance(mesh, (str, Path)):
+        from . import _native
+
+        return _native.runtime().read_stl(str(mesh)).astype(np.float64)
+    if isinstance(mesh, tuple) and len(mesh) == 2:
+        vertices, faces = np.asarray(mesh[0], dtype=np.float64), np.asarray(mesh[1])
+        if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3 \
+                or faces.dtype.kind not in "iu":
+            raise ValueError(f"voxelize(): a (vertices, faces) pair is float [V, 3] and integer [F, 3], not "
+                             f"{vertices.shape} and {faces.dtype} {faces.shape}")
+        if faces.size and (faces.min() < 0 or faces.max() >= len(vertices)):
+            raise ValueError(f"voxelize(): a face names a vertex outside 0..{len(vertices) - 1}")
+        return vertices[faces]
+    tris = np.asarray(mesh.cpu() if isinstance(mesh, torch.Tensor) else mesh, dtype=np.float64)
+    if tris.ndim != 3 or tris.shape[1:] != (3, 3):
+        raise ValueError(f"voxelize(): a mesh is an STL path, a (vertices, faces) pair or an [F, 3, 3] array, not an "
+                         f"array of shape {tris.shape}")
+    return tris
+
+
+def voxelize(meshes, size: int = 64, fit="bbox", margin: float = 0, device=None, packed: bool = False,
+             return_info: bool = False):
+    """Triangle meshes -> occupancy uint8 ``[N, S, S, S]`` (1 = material, indexed ``[n, z, y, x]``),
+    or with ``packed`` its bits, uint8 ``[N, S^3 / 8]``: the input of :func:`classify`,
+    :func:`segment` and :func:`extract_features` from a CAD part's STL file.
+
+    ``meshes`` is an STL path, a ``(vertices [V, 3], faces [F, 3])`` pair, an ``[F, 3, 3]`` array
+    of triangles, or a list of those.  Each mesh is placed on the grid by ``fit``: ``"bbox"``
+    scales it so that the longest side of its bounding box spans the grid less ``margin`` voxels
+    at either end and centres the other axes; ``(origin, voxel_size)`` puts voxel ``(x, y, z)`` at
+    ``origin + voxel_size * (x, y, z)``.  Vertices are snapped to a lattice of 1/16 voxel on the
+    host; from there on everything is integer arithmetic -- a voxel is material when a ray along
+    +x has crossed the surface an odd number of times before its centre, with a tie rule that
+    keeps closed meshes closed -- so the result is the same on every device: ``device`` (default:
+    the GPU when there is one) only chooses between the ``voxelize_tris`` kernel and the host path.
+
+    ``return_info`` adds a dict: ``leaks`` int64 ``[N]``, the columns of each mesh whose ray leaves
+    the grid inside the part (0 for a watertight mesh), and ``origin`` float64 ``[N, 3]`` and
+    ``voxel_size`` float64 ``[N]``, the transforms used (what a binvox header holds).
+    """
+    from .ops import voxelize as vx
+
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    single = isinstance(meshes, (str, Path, np.ndarray, torch.Tensor)) or \
+        (isinstance(meshes, tuple) and len(meshes) == 2 and not isinstance(meshes[0], (str, Path, tuple)))
+    if single and isinstance(meshes, (np.ndarray, torch.Tensor)) and meshes.ndim == 4:
+        single, meshes = False, list(meshes)             # [N, F, 3, 3]: N meshes of F triangles
+    lattice, origins, sizes = [], [], []
+    for mesh in ([meshes] if single else list(meshes)):
+        q, origin, voxel_size = vx.quantize(_mesh_triangles(mesh), size, fit, margin)
+        lattice.append(q.reshape(-1, 9))
+        origins.append(origin)
+        sizes.append(voxel_size)
+    counts = [len(q) for q in lattice]
+    tris = torch.from_numpy(np.concatenate(lattice) if lattice else np.zeros((0, 9), np.int32))
+    offsets = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32)
+    vox, leaks = vx.voxelize(tris, offsets, size, device=device, packed=packed)
+    vox = vox.cpu().numpy()
+    if not return_info:
+        return vox
+    return vox, {"leaks": leaks.cpu().numpy(), "origin": np.asarray(origins, np.float64).reshape(-1, 3),
+                 "voxel_size": np.asarray(sizes, np.float64)}
+
+
 def evaluate(model, x, y, batch_size: int = 256, packed_size: int | None = None) -> float:
     labels, _ = classify(model, x, batch_size, packed_size=packed_size)
     return float((labels == np.asarray(y)).mean())

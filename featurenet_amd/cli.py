@@ -291,6 +291,53 @@ def cmd_generate_parts(a) -> int:
     return 0
 
 
+def cmd_voxelize(a) -> int:
+    import numpy as np
+
+    from . import _native, api
+
+    fit = "bbox" if a.voxel_size is None else (a.origin, a.voxel_size)
+    voxels, info = api.voxelize(list(a.meshes), size=a.size, fit=fit, margin=a.margin, device=a.device or None,
+                                return_info=True)
+    np.save(a.output, voxels)
+    doc = {"shape": list(voxels.shape), "meshes": list(a.meshes), "filled_voxels": voxels.reshape(len(voxels), -1)
+           .sum(1).tolist(), "leaks": info["leaks"].tolist(), "origin": info["origin"].tolist(),
+           "voxel_size": info["voxel_size"].tolist()}
+    if a.binvox:
+        os.makedirs(a.binvox, exist_ok=True)
+        for path, vox, origin, vs in zip(a.meshes, voxels, info["origin"], info["voxel_size"]):
+            stem = os.path.splitext(os.path.basename(path))[0]
+            _native.runtime().write_binvox(os.path.join(a.binvox, stem + ".binvox"), vox, list(origin), vs * a.size)
+    summary = json.dumps(doc)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(summary + "\n")
+    print(summary)
+    return 0
+
+
+def cmd_export_stl(a) -> int:
+    import numpy as np
+
+    from . import _native
+    from .utils.voxelmesh import voxels_to_mesh
+
+    x = np.load(a.input, allow_pickle=False)
+    if x.ndim == 5 and x.shape[-1] == 1:
+        x = x[..., 0]
+    if x.ndim == 4:
+        if not 0 <= a.index < len(x):
+            raise SystemExit(f"export-stl: --index {a.index} outside 0..{len(x) - 1}")
+        x = x[a.index]
+    if x.ndim != 3:
+        raise SystemExit(f"export-stl: {a.input} holds an array of shape {x.shape}, not [S, S, S] or [N, S, S, S]")
+    solid = x == a.value if a.value is not None else x != 0
+    tris = voxels_to_mesh(solid) * a.voxel_size + np.asarray(a.origin, np.float32)
+    _native.runtime().write_stl(a.output, tris.astype(np.float32), not a.ascii)
+    print(json.dumps({"triangles": int(len(tris)), "voxels": int(solid.sum()), "output": a.output}))
+    return 0
+
+
 def cmd_extend(a) -> int:
     from .fm.extend import generate_featuretree
 
@@ -482,6 +529,31 @@ def build_parser() -> argparse.ArgumentParser:
     gp.add_argument("-o", "--output", required=True, help="voxels and labels, uint8 [N, S, S, S] each (.npz)")
     gp.add_argument("--json", default="", metavar="OUT", help="also write the per-part feature lists to this file")
     gp.set_defaults(fn=cmd_generate_parts)
+
+    vx = sub.add_parser("voxelize", help="STL meshes -> occupancy .npy (the input of classify / segment / features)")
+    vx.add_argument("meshes", nargs="+", help="binary or ASCII STL files")
+    vx.add_argument("--size", type=int, default=64, help="grid edge (a multiple of 8, at most 256)")
+    vx.add_argument("--margin", type=float, default=0, help="empty voxels at either end of the longest side")
+    vx.add_argument("--origin", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"),
+                    help="with --voxel-size: the model-space corner of voxel (0, 0, 0)")
+    vx.add_argument("--voxel-size", type=float, default=None,
+                    help="edge of a voxel in model units (default: fit each mesh's bounding box to the grid)")
+    vx.add_argument("--device", default="", help="cuda / cpu (default: the GPU when there is one)")
+    vx.add_argument("-o", "--output", required=True, help="occupancy, uint8 [N, S, S, S] (.npy)")
+    vx.add_argument("--json", default="", metavar="OUT", help="also write leaks and transforms to this file")
+    vx.add_argument("--binvox", default="", metavar="DIR", help="also write one .binvox per mesh into this folder")
+    vx.set_defaults(fn=cmd_voxelize)
+
+    xs = sub.add_parser("export-stl", help="boundary of a voxel volume (.npy) -> STL")
+    xs.add_argument("input", help="[S, S, S] or [N, S, S, S] array (.npy)")
+    xs.add_argument("-o", "--output", required=True)
+    xs.add_argument("--index", type=int, default=0, help="which volume of an [N, S, S, S] array")
+    xs.add_argument("--value", type=int, default=None,
+                    help="export the voxels equal to this value (a label or an instance id; default: every non-zero one)")
+    xs.add_argument("--origin", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"))
+    xs.add_argument("--voxel-size", type=float, default=1.0)
+    xs.add_argument("--ascii", action="store_true")
+    xs.set_defaults(fn=cmd_export_stl)
 
     e = sub.add_parser("extend", help="expand the 1-block template to B x C")
     e.add_argument("--input", default="")

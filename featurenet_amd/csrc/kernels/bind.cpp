@@ -47,6 +47,8 @@ int fn_ccl_flatten(void*, void*, int, int, int, int, hipStream_t);
 int fn_ccl_stats(const void*, const void*, const void*, void*, void*, int, int, int, int, long long, hipStream_t);
 int fn_partgen_chunk();
 int fn_partgen_carve(const void*, void*, void*, void*, void*, int, int, int, hipStream_t);
+int fn_voxelize_planes(int);
+int fn_voxelize_tris(const void*, const void*, void*, void*, void*, int, int, int, int, hipStream_t);
 void fn_overlap_chunk(int*);
 int fn_overlap_pairs(const void*, const void*, const void*, const void*, void*, void*, void*, int, long long, int,
                      long long, long long, hipStream_t);
@@ -756,6 +758,32 @@ PYBIND11_MODULE(_C, m) {
         "partgen_carve");
   }, py::arg("params"), py::arg("occ"), py::arg("packed"), py::arg("labels"), py::arg("slots"), py::arg("N"),
      py::arg("K"), py::arg("S"), py::arg("st"), py::arg("ext"));
+  // triangle meshes to voxel grids (voxelize.hip): tris int32 [T][9] on the 16-units-per-voxel lattice, offsets
+  // int32 [N + 1]; occ uint8 [N][S][S][S] (8-byte aligned), packed uint8 [N][S^3/8] and leaks_part int32
+  // [N][ceil(S / zs)], each 0 = not wanted; zs z-planes per workgroup, 0 = voxelize_planes(S); ext = {numel(tris),
+  // numel(offsets), numel(occ), numel(packed), numel(leaks_part)}
+  m.def("voxelize_planes", [](int size) {
+    const int zs = fn_voxelize_planes(size);
+    chk(zs < 0 ? zs : 0, "voxelize_planes");
+    return zs;
+  }, py::arg("S"));
+  m.def("voxelize_tris", [](uintptr_t tris, uintptr_t offsets, uintptr_t occ, uintptr_t packed, uintptr_t leaks_part,
+                            int N, int T, int size, int zs, uintptr_t st, std::vector<long long> ext) {
+    const long long vox = prod({N, size, size, size});
+    fits(ext, 0, prod({T, 9}), "voxelize_tris", "tris");
+    fits(ext, 1, N < 0 ? -1 : N + 1LL, "voxelize_tris", "offsets");
+    if (occ) fits(ext, 2, vox, "voxelize_tris", "occ");
+    if (packed) fits(ext, 3, vox < 0 ? -1 : vox / 8, "voxelize_tris", "packed");
+    if (leaks_part) {
+      const int planes = zs > 0 ? zs : fn_voxelize_planes(size);
+      fits(ext, 4, planes <= 0 || size <= 0 ? -1 : prod({N, (size + planes - 1) / planes}), "voxelize_tris",
+           "leaks_part");
+    }
+    chk(fn_voxelize_tris(P<const void*>(tris), P<const void*>(offsets), P<void*>(occ), P<void*>(packed),
+                         P<void*>(leaks_part), N, T, size, zs, S(st)),
+        "voxelize_tris");
+  }, py::arg("tris"), py::arg("offsets"), py::arg("occ"), py::arg("packed"), py::arg("leaks_part"), py::arg("N"),
+     py::arg("T"), py::arg("S"), py::arg("zs"), py::arg("st"), py::arg("ext"));
   // part: fp32 scratch of pw_wgrad_blocks(M, K, N) x N x K floats (per-workgroup partials)
   m.def("pw_wgrad", [](uintptr_t dy, uintptr_t x, uintptr_t dw, long long M, int K, int N, uintptr_t st,
                        uintptr_t psc, uintptr_t psh, int pact, uintptr_t part, long long part_n) {

@@ -1,0 +1,220 @@
+// Triangle meshes: the host path of the voxelizer (../shared/voxelize.h has the lattice and the
+// rule; the GPU path is kernels/voxelize.hip) and STL files in and out.
+//
+//   voxelize_tris(tris int32 [T, 9], offsets int32 [N + 1], size, threads)
+//       -> (occupancy uint8 [N, S, S, S], leaks int64 [N])
+//   read_stl(path) -> float32 [F, 3, 3]; write_stl(path, tris, binary = true)
+//
+// A binary STL is 80 header bytes, a uint32 triangle count n and n records of 50 bytes (normal,
+// three vertices, two attribute bytes): a file is binary iff its size is 84 + 50 n -- plenty of
+// binary files begin with "solid".  Anything else must parse as an ASCII STL from "solid" to
+// "endsolid".
+#include <pybind11/numpy.h>
+#include <pybind11/pybind11.h>
+
+#include <algorithm>
+#include <cctype>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <stdexcept>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../shared/voxelize.h"
+#include "parallel_for.h"
+
+namespace py = pybind11;
+
+namespace {
+
+constexpr int kSlabs = 8;              // work items per mesh (S % 8 == 0): one mesh still uses 8 threads
+
+py::tuple voxelize_tris(py::array_t<int32_t, py::array::c_style | py::array::forcecast> tris,
+                        py::array_t<int32_t, py::array::c_style | py::array::forcecast> offsets, int size,
+                        int threads) {
+  if (tris.ndim() != 2 || tris.shape(1) != 9) throw std::runtime_error("voxelize_tris: tris must be int32 [T, 9]");
+  if (offsets.ndim() != 1 || offsets.shape(0) < 1) throw std::runtime_error("voxelize_tris: offsets must be int32 [N + 1]");
+  if (size < 8 || size > VX_MAX_S || size % 8 != 0)
+    throw std::runtime_error("voxelize_tris: size must be a multiple of 8 in [8, 256]");
+  const int N = (int)offsets.shape(0) - 1, S = size;
+  const long long T = tris.shape(0);
+  const int32_t* off = offsets.data();
+  const int32_t* tr = tris.data();
+  if (off[0] != 0 || off[N] != T) throw std::runtime_error("voxelize_tris: offsets must run from 0 to T");
+  for (int n = 0; n < N; ++n)
+    if (off[n + 1] < off[n]) throw std::runtime_error("voxelize_tris: offsets must not decrease");
+  for (long long i = 0; i < T * 9; ++i)
+    if (tr[i] > VX_MAX_COORD || tr[i] < -VX_MAX_COORD)
+      throw std::runtime_error("voxelize_tris: a coordinate exceeds 8192 lattice units");
+  py::array_t<uint8_t> occ(std::vector<py::ssize_t>{N, S, S, S});
+  py::array_t<int64_t> leaks((py::ssize_t)N);
+  uint8_t* po = occ.mutable_data();
+  int64_t* pl = leaks.mutable_data();
+  std::vector<int64_t> part((size_t)N * kSlabs, 0);
+  {
+    py::gil_scoped_release nogil;
+    const int zs = S / kSlabs;
+    parallel_for(N * kSlabs, threads, [&](int item) {
+      const int n = item / kSlabs, zlo = (item % kSlabs) * zs, zhi = zlo + zs - 1;
+      uint8_t* vol = po + (size_t)n * S * S * S;           // toggles first, then their prefix parity
+      std::memset(vol + (size_t)zlo * S * S, 0, (size_t)zs * S * S);
+      std::vector<uint8_t> over((size_t)zs * S, 0);
+      VxTri t;
+      for (int i = off[n]; i < off[n + 1]; ++i) {
+        if (!vx_setup(tr + (size_t)i * 9, S, zlo, zhi, t)) continue;
+        for (int iz = t.z0; iz <= t.z1; ++iz)
+          for (int iy = t.y0; iy <= t.y1; ++iy) {
+            if (!vx_covers(t, iy, iz)) continue;
+            const int k = vx_kmin(t, S, iy, iz);
+            if (k < S) vol[((size_t)iz * S + iy) * S + k] ^= 1;
+            else over[(size_t)(iz - zlo) * S + iy] ^= 1;
+          }
+      }
+      int64_t odd = 0;
+      for (int iz = zlo; iz <= zhi; ++iz)
+        for (int iy = 0; iy < S; ++iy) {
+          uint8_t* col = vol + ((size_t)iz * S + iy) * S;
+          uint8_t in = 0;
+          for (int k = 0; k < S; ++k) col[k] = in ^= col[k];
+          odd += in ^ over[(size_t)(iz - zlo) * S + iy];
+        }
+      part[item] = odd;
+    });
+  }
+  for (int n = 0; n < N; ++n) {
+    pl[n] = 0;
+    for (int s = 0; s < kSlabs; ++s) pl[n] += part[(size_t)n * kSlabs + s];
+  }
+  return py::make_tuple(occ, leaks);
+}
+
+// ---------------------------------------------------------------------------------------------
+// STL
+// ---------------------------------------------------------------------------------------------
+std::string slurp(const std::string& path) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) throw std::runtime_error("cannot open " + path);
+  return std::string((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+}
+
+py::array_t<float> tri_array(const std::vector<float>& v) {
+  py::array_t<float> out(std::vector<py::ssize_t>{(py::ssize_t)(v.size() / 9), 3, 3});
+  if (!v.empty()) std::memcpy(out.mutable_data(), v.data(), v.size() * sizeof(float));
+  return out;
+}
+
+py::array_t<float> read_stl(const std::string& path) {
+  const std::string buf = slurp(path);
+  std::vector<float> v;
+  if (buf.size() >= 84) {
+    uint32_t n;
+    std::memcpy(&n, buf.data() + 80, 4);
+    if ((uint64_t)buf.size() == 84 + 50ull * n) {
+      v.resize((size_t)n * 9);
+      for (size_t i = 0; i < n; ++i) std::memcpy(&v[i * 9], buf.data() + 84 + i * 50 + 12, 36);
+      for (float x : v)
+        if (!std::isfinite(x)) throw std::runtime_error("read_stl: " + path + " holds a coordinate that is not finite");
+      return tri_array(v);
+    }
+  }
+  // ASCII: solid [name] { facet normal x y z / outer loop / 3 x vertex x y z / endloop / endfacet } endsolid
+  size_t p = 0;
+  auto token = [&]() -> std::string {
+    while (p < buf.size() && std::isspace((unsigned char)buf[p])) ++p;
+    const size_t b = p;
+    while (p < buf.size() && !std::isspace((unsigned char)buf[p])) ++p;
+    return buf.substr(b, p - b);
+  };
+  auto number = [&]() -> float {
+    const std::string s = token();
+    char* end = nullptr;
+    const float x = std::strtof(s.c_str(), &end);
+    if (s.empty() || end != s.c_str() + s.size() || !std::isfinite(x))
+      throw std::runtime_error("read_stl: " + path + ": '" + s + "' is not a coordinate");
+    return x;
+  };
+  if (token() != "solid")
+    throw std::runtime_error("read_stl: " + path + " is neither a binary STL (its size is not 84 + 50 n bytes) nor an ASCII one");
+  while (p < buf.size() && buf[p] != '\n') ++p;            // the rest of the line is the name
+  bool closed = false;
+  for (;;) {
+    const std::string t = token();
+    if (t == "endsolid") { closed = true; break; }
+    if (t.empty()) break;
+    if (t != "facet") throw std::runtime_error("read_stl: " + path + ": expected 'facet', found '" + t + "'");
+    if (token() != "normal") throw std::runtime_error("read_stl: " + path + ": expected 'normal'");
+    for (int i = 0; i < 3; ++i) number();
+    if (token() != "outer" || token() != "loop") throw std::runtime_error("read_stl: " + path + ": expected 'outer loop'");
+    for (int c = 0; c < 3; ++c) {
+      if (token() != "vertex") throw std::runtime_error("read_stl: " + path + ": expected 'vertex'");
+      for (int i = 0; i < 3; ++i) v.push_back(number());
+    }
+    if (token() != "endloop" || token() != "endfacet")
+      throw std::runtime_error("read_stl: " + path + ": expected 'endloop endfacet'");
+  }
+  if (!closed) throw std::runtime_error("read_stl: " + path + " ends before 'endsolid'");
+  return tri_array(v);
+}
+
+void write_stl(const std::string& path, py::array_t<float, py::array::c_style | py::array::forcecast> tris, bool binary) {
+  if (tris.ndim() != 3 || tris.shape(1) != 3 || tris.shape(2) != 3)
+    throw std::runtime_error("write_stl: tris must be [F, 3, 3]");
+  const size_t n = (size_t)tris.shape(0);
+  if (n > 0xffffffffull) throw std::runtime_error("write_stl: too many triangles");
+  const float* t = tris.data();
+  std::ofstream f(path, std::ios::binary);
+  if (!f) throw std::runtime_error("cannot open " + path);
+  auto normal = [&](size_t i, float* nrm) {
+    const float* a = t + i * 9;
+    const double u[3] = {(double)a[3] - a[0], (double)a[4] - a[1], (double)a[5] - a[2]};
+    const double w[3] = {(double)a[6] - a[0], (double)a[7] - a[1], (double)a[8] - a[2]};
+    double c[3] = {u[1] * w[2] - u[2] * w[1], u[2] * w[0] - u[0] * w[2], u[0] * w[1] - u[1] * w[0]};
+    const double len = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+    for (int d = 0; d < 3; ++d) nrm[d] = len > 0 ? (float)(c[d] / len) : 0.f;
+  };
+  float nrm[3];
+  if (binary) {
+    char head[80] = "featurenet_amd binary STL";                  // (must not matter to a reader)
+    f.write(head, 80);
+    const uint32_t cnt = (uint32_t)n;
+    f.write(reinterpret_cast<const char*>(&cnt), 4);
+    char rec[50];
+    for (size_t i = 0; i < n; ++i) {
+      normal(i, nrm);
+      std::memcpy(rec, nrm, 12);
+      std::memcpy(rec + 12, t + i * 9, 36);
+      rec[48] = rec[49] = 0;
+      f.write(rec, 50);
+    }
+  } else {
+    char line[256];
+    f << "solid featurenet_amd\n";
+    for (size_t i = 0; i < n; ++i) {
+      normal(i, nrm);
+      std::snprintf(line, sizeof line, "facet normal %.9g %.9g %.9g\n outer loop\n", nrm[0], nrm[1], nrm[2]);
+      f << line;
+      for (int c = 0; c < 3; ++c) {
+        std::snprintf(line, sizeof line, "  vertex %.9g %.9g %.9g\n", t[i * 9 + c * 3], t[i * 9 + c * 3 + 1], t[i * 9 + c * 3 + 2]);
+        f << line;
+      }
+      f << " endloop\nendfacet\n";
+    }
+    f << "endsolid featurenet_amd\n";
+  }
+  if (!f) throw std::runtime_error("write_stl: could not write " + path);
+}
+
+}  // namespace
+
+void register_mesh(py::module_& m) {
+  m.def("voxelize_tris", &voxelize_tris, py::arg("tris"), py::arg("offsets"), py::arg("size"), py::arg("threads") = 0,
+        "meshes on the 16-units-per-voxel lattice, int32 [T, 9] + offsets int32 [N + 1] -> (occupancy uint8 "
+        "[N, S, S, S], leaks int64 [N])");
+  m.def("read_stl", &read_stl, py::arg("path"), "binary or ASCII STL -> float32 [F, 3, 3]");
+  m.def("write_stl", &write_stl, py::arg("path"), py::arg("tris"), py::arg("binary") = true);
+}

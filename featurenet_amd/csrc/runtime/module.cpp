@@ -3,6 +3,7 @@
 
 namespace py = pybind11;
 
+void register_mesh(py::module_& m);
 void register_sampler(py::module_& m);
 void register_voxel(py::module_& m);
 void register_weibull(py::module_& m);
@@ -12,4 +13,5 @@ PYBIND11_MODULE(_rt, m) {
   register_sampler(m);
   register_voxel(m);
   register_weibull(m);
+  register_mesh(m);
 }

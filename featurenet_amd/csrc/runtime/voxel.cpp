@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "../shared/partgen.h"
+#include "parallel_for.h"
 
 namespace py = pybind11;
 
@@ -497,18 +498,6 @@ int sample_one(int S, uint64_t seed, int lo_n, int hi_n, int num_classes, bool s
     for (int f = 0; f < PG_ROW; ++f)
       rows[k * PG_ROW + f] = k < best_n ? best[(size_t)k * PG_ROW + f] : (f == PG_CLS ? -1 : 0);
   return std::max(best_n, 0);
-}
-
-template <typename F>
-void parallel_for(int n, int threads, F&& body) {
-  if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
-  threads = std::min(threads, std::max(1, n));
-  std::vector<std::thread> pool;
-  for (int t = 0; t < threads; ++t)
-    pool.emplace_back([&, t]() {
-      for (int i = t; i < n; i += threads) body(i);
-    });
-  for (auto& th : pool) th.join();
 }
 
 py::array_t<int32_t> sample_parts(int n, int size, uint64_t seed, int min_features, int max_features,

@@ -360,3 +360,59 @@ def carve_parts(params: torch.Tensor, size: int):
                 labels[sel] = torch.where(vol, torch.full_like(labels[sel], cls + 1), labels[sel])
                 slots[sel] = torch.where(vol, torch.full_like(slots[sel], k + 1), slots[sel])
     return (labels == 0).to(torch.uint8), labels, slots
+
+
+def voxelize_tris(tris: torch.Tensor, offsets: torch.Tensor, size: int):
+    """Triangle meshes to voxel grids -> ``(occupancy uint8 [N, S, S, S], leaks int64 [N])`` on the
+    device of ``tris``.
+
+    ``tris`` int32 ``[T, 9]`` (``ax ay az bx by bz cx cy cz``) on the lattice of 16 units per voxel
+    (voxel ``k`` of an axis has its centre at ``16 k + 8``, every ``|coordinate| <= 8192``) and
+    ``offsets`` int32 ``[N + 1]``: mesh ``n`` owns ``tris[offsets[n]:offsets[n + 1]]``.  A ray
+    runs along +x through every column centre ``(py, pz)``.  A triangle whose ``(y, z)`` projection
+    has area covers the columns whose centre has all three edge functions (taken with the
+    projection turned counter-clockwise) positive, or zero on an edge that runs towards +y, or
+    straight towards -z (the low-z and low-y edges of the projection); the ray crosses its plane at ``x_hit`` and toggles the first voxel
+    ``k >= 0`` whose centre is not left of ``x_hit`` (``k = S``: beyond the grid).  A voxel is
+    material when the toggles at or left of it are odd in number; ``leaks`` counts the columns
+    whose toggles, those beyond the grid included, are odd -- 0 for a closed mesh.  Exact integers
+    (int64 throughout): the oracle of ``voxelize_tris`` (kernel) and ``_rt.voxelize_tris``."""
+    if tris.dim() != 2 or tris.shape[1] != 9 or tris.dtype != torch.int32:
+        raise ValueError(f"voxelize_tris: tris must be int32 [T, 9], not {tris.dtype} {tuple(tris.shape)}")
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("voxelize_tris: offsets must be [N + 1]")
+    S, dev = int(size), tris.device
+    off = [int(v) for v in offsets.tolist()]
+    N = len(off) - 1
+    occ = torch.zeros(N, S, S, S, dtype=torch.uint8, device=dev)
+    leaks = torch.zeros(N, dtype=torch.int64, device=dev)
+    centre = 16 * torch.arange(S, device=dev, dtype=torch.int64) + 8
+    pz, py = (c.reshape(1, -1) for c in torch.meshgrid(centre, centre, indexing="ij"))      # [1, S*S], column = z*S + y
+    chunk = max(1, (1 << 21) // (S * S))
+    for n in range(N):
+        counts = torch.zeros(S * S * (S + 1), dtype=torch.int64, device=dev)
+        for lo in range(off[n], off[n + 1], chunk):
+            t = tris[lo:min(lo + chunk, off[n + 1])].to(torch.int64)
+            a, b, c = t[:, 0:3], t[:, 3:6], t[:, 6:9]
+            area2 = (b[:, 1] - a[:, 1]) * (c[:, 2] - a[:, 2]) - (b[:, 2] - a[:, 2]) * (c[:, 1] - a[:, 1])
+            flip = (area2 < 0).unsqueeze(1)
+            b, c = torch.where(flip, c, b), torch.where(flip, b, c)
+            keep = area2 != 0
+            a, b, c = a[keep], b[keep], c[keep]
+            if not len(a):
+                continue
+            inside = torch.ones(len(a), S * S, dtype=torch.bool, device=dev)
+            for p, q in ((a, b), (b, c), (c, a)):
+                dy, dz = (q[:, 1] - p[:, 1]).unsqueeze(1), (q[:, 2] - p[:, 2]).unsqueeze(1)
+                E = dy * (pz - p[:, 2:3]) - dz * (py - p[:, 1:2])
+                inside &= (E > 0) | ((E == 0) & ((dy > 0) | ((dy == 0) & (dz < 0))))
+            nrm = torch.linalg.cross(b - a, c - a)                          # nrm[:, 0] = |area2| > 0
+            ti, col = inside.nonzero(as_tuple=True)
+            nx = nrm[ti, 0]
+            A = nrm[ti, 1] * (py[0, col] - a[ti, 1]) + nrm[ti, 2] * (pz[0, col] - a[ti, 2])
+            k = -torch.div(-(a[ti, 0] * nx - A - 8 * nx), 16 * nx, rounding_mode="floor")      # ceil
+            counts += torch.bincount(col * (S + 1) + k.clamp(0, S), minlength=counts.numel())
+        odd = (counts.view(S, S, S + 1) % 2).cumsum(-1) % 2
+        occ[n] = odd[..., :S].to(torch.uint8)
+        leaks[n] = odd[..., S].sum()
+    return occ, leaks
