@@ -280,7 +280,7 @@ def evaluate_segmentation(model, x, y, batch_size: int = 32, device=None, packed
 @torch.no_grad()
 def extract_features(model, x, batch_size: int = 32, device=None, packed_size: int | None = None,
                      background: int | None = 0, connectivity: int = 6, min_voxels: int = 1,
-                     return_ids: bool = False):
+                     return_ids: bool = False, access: bool = False):
     """The machining features of each part -> (one list of :class:`FeatureInstance` per sample,
     ids int32 [N, S, S, S] or None).
 
@@ -291,6 +291,12 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
     to the host, plus, with ``return_ids``, the volume that numbers each sample's components from
     1 in raster order of their first voxel.  ``min_voxels`` drops smaller components from the lists
     only: the others keep their ``id``, and ``ids`` keeps every component.
+
+    With ``access`` every record also says from which faces of the grid the feature is reached
+    (``FeatureInstance.access``, ``open_faces()``, ``through``, ``enclosed``): a voxel is open
+    toward ``+x`` when no material (``x != 0``) lies beyond it in its x column, and so on for the
+    six faces ``+z, -z, +x, -x, +y, -y`` (``+z`` is the high-index end of z).  The counts are made
+    on the model's device (``ops.access``); 8 more integers per component cross to the host.
     """
     from .utils.seginstances import FeatureInstance
 
@@ -312,9 +318,9 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
         if packed_size is not None:
             xb = unpack_voxels(xb, packed_size)
         xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
-        table, offsets, idb = model.instances(xb, background=background, connectivity=connectivity,
-                                              want_ids=return_ids)
-        feats += FeatureInstance.from_table(table, offsets, min_voxels)
+        table, offsets, idb, *acc = model.instances(xb, background=background, connectivity=connectivity,
+                                                    want_ids=return_ids, want_access=access)
+        feats += FeatureInstance.from_table(table, offsets, min_voxels, access=acc[0] if access else None)
         if return_ids:
             ids.append(idb.cpu())
     if not return_ids:
@@ -324,15 +330,17 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
 
 
 @torch.no_grad()
-def label_components(labels, background: int | None = 0, connectivity: int = 6, device=None):
+def label_components(labels, background: int | None = 0, connectivity: int = 6, device=None, occupancy=None):
     """Connected components of label volumes the caller already has (ground truth, say) ->
     (ids int32 [N, D, H, W], one list of :class:`FeatureInstance` per sample).
 
     ``labels`` is ``[N, D, H, W]`` of any integer dtype with values
     0..255; ``background`` and ``connectivity`` as for :func:`extract_features`.  ``device``
     defaults to the GPU when there is one (the ``ccl`` kernels), else the CPU reference path.
+    ``occupancy``, an integer or bool array of the labels' shape (material: non-zero), adds the
+    access counts to the records as :func:`extract_features` does with ``access``.
     """
-    from .ops import ccl
+    from .ops import access, ccl
     from .utils.seginstances import FeatureInstance
 
     lt = torch.as_tensor(np.asarray(labels)) if not isinstance(labels, torch.Tensor) else labels
@@ -346,10 +354,20 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
         raise ValueError("label_components(): label values must lie in 0..255")
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
+    ot = None
+    if occupancy is not None:
+        ot = torch.as_tensor(np.asarray(occupancy)) if not isinstance(occupancy, torch.Tensor) else occupancy
+        if ot.is_floating_point() or ot.is_complex():
+            raise ValueError(f"label_components(): occupancy must be integers or bools, not {ot.dtype}")
+        if ot.shape != lt.shape:
+            raise ValueError(f"label_components(): occupancy is {tuple(ot.shape)} but labels {tuple(lt.shape)}")
     lt = lt.to(device).to(torch.uint8).contiguous()
     roots, flags = ccl.connected_components(lt, background, connectivity, return_flags=True)
     ids, table, offsets = ccl.instance_table(lt, roots, want_ids=True, flags=flags)
-    return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets)
+    acc = None
+    if ot is not None:
+        acc, _ = access.access_table(ids, offsets, (ot.to(device) != 0).to(torch.uint8), rows=table.shape[0])
+    return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets, access=acc)
 
 
 def _label_volumes(labels, what: str, name: str = "labels") -> torch.Tensor:

@@ -245,10 +245,11 @@ def cmd_features(a) -> int:
     x = np.load(a.input, allow_pickle=False)
     feats, ids = api.extract_features(a.model, x, packed_size=a.packed_size,
                                       background=None if a.background < 0 else a.background,
-                                      connectivity=a.connectivity, min_voxels=a.min_voxels, return_ids=bool(a.ids))
+                                      connectivity=a.connectivity, min_voxels=a.min_voxels, return_ids=bool(a.ids),
+                                      access=a.access)
     if a.ids:
         np.save(a.ids, ids)
-    summary = json.dumps({"samples": [[f.to_dict() for f in fs] for fs in feats]})
+    summary = json.dumps({"samples": [[f.to_dict(a.access_fraction) for f in fs] for fs in feats]})
     if a.json:
         with open(a.json, "w") as f:
             f.write(summary + "\n")
@@ -501,6 +502,11 @@ def build_parser() -> argparse.ArgumentParser:
     ft.add_argument("--connectivity", type=int, default=6, choices=(6, 26))
     ft.add_argument("--min-voxels", type=int, default=1, metavar="K", help="leave out smaller instances")
     ft.add_argument("--packed-size", type=int, default=None)
+    ft.add_argument("--access", action="store_true",
+                    help="add the access directions: voxels open toward each face (+z -z +x -x +y -y), open_faces, "
+                         "through, enclosed")
+    ft.add_argument("--access-fraction", type=float, default=1.0, metavar="F",
+                    help="with --access: a face is open when at least this fraction of the voxels is (default 1.0)")
     ft.set_defaults(fn=cmd_features)
 
     sf = sub.add_parser("score-features", help="match the predicted feature instances of a segmentation checkpoint "

@@ -52,6 +52,10 @@ int fn_voxelize_tris(const void*, const void*, void*, void*, void*, int, int, in
 void fn_overlap_chunk(int*);
 int fn_overlap_pairs(const void*, const void*, const void*, const void*, void*, void*, void*, int, long long, int,
                      long long, long long, hipStream_t);
+void fn_access_chunk(int*);
+int fn_access_extents(const void*, void*, void*, void*, int, int, int, int, hipStream_t);
+int fn_access_stats(const void*, const void*, const void*, const void*, const void*, void*, void*, int, int, int, int,
+                    long long, hipStream_t);
 int fn_pw_wgrad(const void*, const void*, float*, long long, int, int, hipStream_t, const float*, const float*, int,
                 float*);
 int fn_pw_wgrad_blocks(long long, int, int);
@@ -741,6 +745,43 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("ids_a"), py::arg("ids_b"), py::arg("off_a"), py::arg("off_b"), py::arg("keys"), py::arg("counts"),
      py::arg("lost"), py::arg("N"), py::arg("V"), py::arg("W"), py::arg("cap"), py::arg("probe"), py::arg("st"),
      py::arg("ext"));
+  // access directions of feature instances (access.hip): occ uint8 [N][D][H][W] (material: != 0); column extents
+  // ex int32 [N][D][H][2], ey [N][D][W][2], ez [N][H][W][2] = (lo, hi) of the material along x / y / z, (axis length,
+  // -1) for an empty column, written in full; ext = {numel(occ), numel(ex), numel(ey), numel(ez)}
+  m.def("access_chunk", []() {
+    int t[2];
+    fn_access_chunk(t);
+    return py::make_tuple(t[0], t[1]);
+  });
+  m.def("access_extents", [](uintptr_t occ, uintptr_t ex, uintptr_t ey, uintptr_t ez, int N, int D, int H, int W,
+                             uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "access_extents", "occ");
+    fits(ext, 1, prod({N, D, H, 2}), "access_extents", "ex");
+    fits(ext, 2, prod({N, D, W, 2}), "access_extents", "ey");
+    fits(ext, 3, prod({N, H, W, 2}), "access_extents", "ez");
+    chk(fn_access_extents(P<const void*>(occ), P<void*>(ex), P<void*>(ey), P<void*>(ez), N, D, H, W, S(st)),
+        "access_extents");
+  }, py::arg("occ"), py::arg("ex"), py::arg("ey"), py::arg("ez"), py::arg("N"), py::arg("D"), py::arg("H"),
+     py::arg("W"), py::arg("st"), py::arg("ext"));
+  // ids int32 [N*V] (per-sample ids from 1, 0 = none), offsets int64 [N+1] (the instance table's), ex / ey / ez as
+  // access_extents writes them; mask uint8 [N*V], 0 = not wanted: bit k = open toward face k (+z -z +x -x +y -y), 0
+  // where ids is 0; acc int64 [T][8] (fully rewritten): voxels open toward each face, toward none, voxels; ext =
+  // {numel(ids), numel(offsets), numel(ex), numel(ey), numel(ez), numel(mask), numel(acc)}
+  m.def("access_stats", [](uintptr_t ids, uintptr_t offsets, uintptr_t ex, uintptr_t ey, uintptr_t ez, uintptr_t mask,
+                           uintptr_t acc, int N, int D, int H, int W, long long T, uintptr_t st,
+                           std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "access_stats", "ids");
+    fits(ext, 1, N < 0 ? -1 : N + 1LL, "access_stats", "offsets");
+    fits(ext, 2, prod({N, D, H, 2}), "access_stats", "ex");
+    fits(ext, 3, prod({N, D, W, 2}), "access_stats", "ey");
+    fits(ext, 4, prod({N, H, W, 2}), "access_stats", "ez");
+    if (mask) fits(ext, 5, prod({N, D, H, W}), "access_stats", "mask");
+    fits(ext, 6, prod({T, 8}), "access_stats", "acc");
+    chk(fn_access_stats(P<const void*>(ids), P<const void*>(offsets), P<const void*>(ex), P<const void*>(ey),
+                        P<const void*>(ez), P<void*>(mask), P<void*>(acc), N, D, H, W, T, S(st)),
+        "access_stats");
+  }, py::arg("ids"), py::arg("offsets"), py::arg("ex"), py::arg("ey"), py::arg("ez"), py::arg("mask"), py::arg("acc"),
+     py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("T"), py::arg("st"), py::arg("ext"));
   // multi-feature parts from their parameter tables (partgen.hip): params int32 [N][K][16]; occ / labels / slots
   // uint8 [N][S][S][S] (8-byte aligned) and packed uint8 [N][S^3/8], each 0 = not wanted; S % 8 == 0, 8 <= S <=
   // 256, K <= 32; ext = {numel(params), numel(occ), numel(packed), numel(labels), numel(slots)}

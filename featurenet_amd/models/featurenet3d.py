@@ -260,22 +260,33 @@ class FeatureNet3DSeg(nn.Module):
 
     @torch.no_grad()
     def instances(self, x: torch.Tensor, background: int | None = 0, connectivity: int = 6,
-                  want_ids: bool = False):
+                  want_ids: bool = False, want_access: bool = False):
         """The features in each sample: :meth:`predict`'s labels split into connected components
         -> ``(table, offsets, ids or None)`` on the model's device.  ``table`` int64 ``[T, 13]``
         has one row per component (``sample, class, voxels, root, z0, y0, x0, z1, y1, x1, sum_z,
         sum_y, sum_x``, sorted by sample and first voxel), sample ``n`` owns rows
         ``offsets[n]:offsets[n + 1]``, ``ids`` int32 ``[N, S, S, S]`` numbers each sample's
         components from 1 (``ops.ccl``).  Voxels of class ``background`` (None: no such class)
-        belong to no component; ``connectivity`` is 6 or 26.  The labels never leave the device."""
-        from ..ops import ccl
+        belong to no component; ``connectivity`` is 6 or 26.  The labels never leave the device.
+
+        With ``want_access`` -> ``(table, offsets, ids or None, acc)``: ``acc`` int64 ``[T, 8]``
+        counts, row by row of ``table``, the component's voxels that are open toward the faces
+        ``+z, -z, +x, -x, +y, -y`` of the grid (no material, ``x != 0``, lies beyond the voxel on
+        that side), toward none, and all of them (``ops.access``)."""
+        from ..ops import access, ccl
 
         if connectivity not in (6, 26):
             raise ValueError(f"instances: connectivity must be 6 or 26, not {connectivity!r}")
         labels = self.predict(x)
         roots, flags = ccl.connected_components(labels, background, connectivity, return_flags=True)
-        ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids, flags=flags)
-        return table, offsets, ids
+        ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids or want_access, flags=flags)
+        if not want_access:
+            return table, offsets, ids
+        occ = (x != 0).to(device=labels.device, dtype=torch.uint8)
+        if occ.dim() == 5:                       # [N, S, S, S, C]: material in any channel
+            occ = occ.amax(-1)
+        acc, _ = access.access_table(ids, offsets, occ.reshape(labels.shape), rows=table.shape[0])
+        return table, offsets, ids if want_ids else None, acc
 
     def match(self, x: torch.Tensor, y: torch.Tensor, background: int | None = 0, connectivity: int = 6):
         """The predicted features against the true ones: the instances of :meth:`predict`'s labels,

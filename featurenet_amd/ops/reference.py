@@ -250,6 +250,68 @@ def overlap_table(ids_a: torch.Tensor, off_a: torch.Tensor, ids_b: torch.Tensor,
     return torch.stack([keys >> 32, keys & 0xffffffff, counts], 1)
 
 
+def column_extents(occ: torch.Tensor):
+    """Column extents of an occupancy volume ``uint8 [N, D, H, W]`` (material: ``occ != 0``) ->
+    ``(ex, ey, ez)`` int32 ``[N, D, H, 2]``, ``[N, D, W, 2]``, ``[N, H, W, 2]``: ``[..., 0]`` is the
+    smallest index along x / y / z that holds material in the column (the axis length when it has
+    none), ``[..., 1]`` the largest (-1 when none).  ``amin`` / ``amax`` over an index grid: the
+    oracle of ``access_extents`` and the CPU path of ``ops.access.column_extents``."""
+    if occ.dim() != 4 or occ.dtype != torch.uint8:
+        raise ValueError(f"column_extents: occ must be uint8 [N, D, H, W], not {occ.dtype} {tuple(occ.shape)}")
+    m = occ != 0
+    out = []
+    for axis in (3, 2, 1):
+        L = occ.shape[axis]
+        rest = [s for a, s in enumerate(occ.shape) if a != axis]
+        if L == 0 or occ.numel() == 0:
+            lo = torch.full(rest, L, dtype=torch.int64, device=occ.device)
+            hi = torch.full(rest, -1, dtype=torch.int64, device=occ.device)
+        else:
+            idx = torch.arange(L, device=occ.device).view([L if a == axis else 1 for a in range(4)])
+            lo = torch.where(m, idx, L).amin(axis)
+            hi = torch.where(m, idx, -1).amax(axis)
+        out.append(torch.stack([lo, hi], -1).to(torch.int32))
+    return tuple(out)
+
+
+def access_table(ids: torch.Tensor, offsets: torch.Tensor, occ: torch.Tensor, want_mask: bool = False):
+    """Access table of an instance-id volume over an occupancy volume -> ``(acc, mask or None)``.
+
+    ``ids`` int32 ``[N, D, H, W]`` and ``offsets`` int64 ``[N + 1]`` as :func:`instance_table`
+    gives them, ``occ`` uint8 of the ids' shape.  A voxel ``(z, y, x)`` is open toward ``+x`` when
+    no material lies strictly beyond it in its x column (``ex hi <= x``), toward ``-x`` when none
+    lies strictly before it (``ex lo >= x``), likewise y and z; its own occupancy does not enter.
+    ``mask`` uint8 ``[N, D, H, W]`` holds bit ``k`` where the voxel is open toward face ``k`` of
+    ``+z, -z, +x, -x, +y, -y`` (0 where ``ids == 0``).  ``acc`` int64 ``[T, 8]``, ``T =
+    offsets[-1]``: row ``offsets[n] + id - 1`` counts, of id ``id`` of sample ``n``, the voxels open
+    toward each face (columns 0..5), toward none (6) and all of them (7).  Exact integers: the
+    oracle of ``access_stats`` and the CPU path of ``ops.access.access_table``."""
+    N, D, H, W = ids.shape
+    dev = ids.device
+    ex, ey, ez = column_extents(occ)
+    z = torch.arange(D, device=dev).view(1, D, 1, 1)
+    y = torch.arange(H, device=dev).view(1, 1, H, 1)
+    x = torch.arange(W, device=dev).view(1, 1, 1, W)
+    open_ = (ez[..., 1].unsqueeze(1) <= z, ez[..., 0].unsqueeze(1) >= z,
+             ex[..., 1].unsqueeze(3) <= x, ex[..., 0].unsqueeze(3) >= x,
+             ey[..., 1].unsqueeze(2) <= y, ey[..., 0].unsqueeze(2) >= y)
+    T = int(offsets[-1])
+    row = ids.to(torch.int64) + offsets.to(torch.int64)[:-1].view(N, 1, 1, 1) - 1
+    fg = (ids > 0) & (row >= 0) & (row < T)
+    mask = torch.zeros(ids.shape, dtype=torch.int64, device=dev)
+    for k, b in enumerate(open_):
+        mask |= b.expand(ids.shape).to(torch.int64) << k
+    mask = torch.where(fg, mask, 0)
+    rows, bits = row[fg], mask[fg]
+    acc = torch.zeros(T, 8, dtype=torch.int64, device=dev)
+    if T:
+        for k in range(6):
+            acc[:, k] = torch.bincount(rows[(bits >> k & 1) != 0], minlength=T)
+        acc[:, 6] = torch.bincount(rows[bits == 0], minlength=T)
+        acc[:, 7] = torch.bincount(rows, minlength=T)
+    return acc, (mask.to(torch.uint8) if want_mask else None)
+
+
 def _part_volume(cls: int, f: dict, X, Y, Z, top: int):
     """The volume of one feature class over canonical quarter-voxel coordinates ``X, Y, Z``
     (int64 ``[n, S, S, S]``); ``f`` maps the field names of a table row to ``[n, 1, 1, 1]``."""

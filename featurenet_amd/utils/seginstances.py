@@ -1,13 +1,18 @@
 """Feature instances: the connected components of a label volume as records.
 
 One :class:`FeatureInstance` per row of the instance table (``ops.ccl.instance_table``): exact
-integer counts and bounds, the centroid as ``sum / voxels`` in float64 on the host.
+integer counts and bounds, the centroid as ``sum / voxels`` in float64 on the host; with an access
+table (``ops.access.access_table``) also the voxels open toward each face of the grid.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
 
 import numpy as np
+
+from .partfeatures import FACES
+
+_AXIS = {"z": 0, "y": 1, "x": 2}
 
 
 @dataclass
@@ -18,19 +23,52 @@ class FeatureInstance:
     voxels: int
     bbox: tuple              # (z0, y0, x0, z1, y1, x1), bounds inclusive
     centroid: tuple          # (z, y, x), float64
+    access: tuple | None = None    # its voxels open toward each face, in FACES order (None: not computed)
+    enclosed: int | None = None    # its voxels open toward no face
 
-    def to_dict(self) -> dict:
-        """JSON-safe record."""
-        return {"id": self.id, "class": self.cls, "voxels": self.voxels, "bbox": list(self.bbox),
-                "centroid": list(self.centroid)}
+    def open_faces(self, min_fraction: float = 1.0) -> tuple:
+        """The names of the faces toward which at least ``min_fraction`` of the voxels are open:
+        no material lies between such a voxel and that face of the grid."""
+        if self.access is None:
+            raise ValueError("open_faces: this instance carries no access counts (extract_features(access=True))")
+        return tuple(f for f, c in zip(FACES, self.access) if c >= min_fraction * self.voxels)
+
+    @property
+    def through(self) -> bool:
+        """Open toward two opposite faces (a through hole or slot); False without access counts."""
+        faces = self.open_faces() if self.access is not None else ()
+        return any(FACES[k] in faces and FACES[k + 1] in faces for k in (0, 2, 4))
+
+    def depth(self, face: str) -> int:
+        """The extent of the bounding box along the axis of ``face`` (``"+z"`` ... ``"-y"``)."""
+        if face not in FACES:
+            raise ValueError(f"depth: face must be one of {FACES}, not {face!r}")
+        a = _AXIS[face[1]]
+        return self.bbox[3 + a] - self.bbox[a] + 1
+
+    def to_dict(self, min_fraction: float = 1.0) -> dict:
+        """JSON-safe record; with access counts also ``access`` (face -> voxels), ``open_faces``
+        (at ``min_fraction``), ``through`` and ``enclosed``."""
+        d = {"id": self.id, "class": self.cls, "voxels": self.voxels, "bbox": list(self.bbox),
+             "centroid": list(self.centroid)}
+        if self.access is not None:
+            d.update(access=dict(zip(FACES, self.access)), open_faces=list(self.open_faces(min_fraction)),
+                     through=self.through, enclosed=self.enclosed)
+        return d
 
     @staticmethod
-    def from_table(table, offsets, min_voxels: int = 1) -> "list[list[FeatureInstance]]":
+    def from_table(table, offsets, min_voxels: int = 1, access=None) -> "list[list[FeatureInstance]]":
         """Per-sample record lists from an instance table int64 ``[T, 13]`` and its ``offsets``
         ``[N + 1]`` (tensors or arrays).  Components of fewer than ``min_voxels`` voxels are left
-        out; the others keep their ``id``."""
+        out; the others keep their ``id``.  ``access``: the access table int64 ``[T, 8]`` of the
+        same rows, or None."""
         tab = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.int64).reshape(-1, 13)
         off = np.asarray(offsets.cpu() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
+        acc = None
+        if access is not None:
+            acc = np.asarray(access.cpu() if hasattr(access, "cpu") else access, dtype=np.int64).reshape(-1, 8)
+            if len(acc) != len(tab) or not np.array_equal(acc[:, 7], tab[:, 2]):
+                raise ValueError("from_table: the access table does not belong to this instance table")
         out = []
         for n in range(len(off) - 1):
             recs = []
@@ -40,8 +78,11 @@ class FeatureInstance:
                 if vox < min_voxels:
                     continue
                 cen = row[10:13].astype(np.float64) / np.float64(vox)
-                recs.append(FeatureInstance(id=k - int(off[n]) + 1, cls=int(row[1]), voxels=vox,
-                                            bbox=tuple(int(v) for v in row[4:10]),
-                                            centroid=tuple(float(c) for c in cen)))
+                rec = FeatureInstance(id=k - int(off[n]) + 1, cls=int(row[1]), voxels=vox,
+                                      bbox=tuple(int(v) for v in row[4:10]),
+                                      centroid=tuple(float(c) for c in cen))
+                if acc is not None:
+                    rec.access, rec.enclosed = tuple(int(c) for c in acc[k, :6]), int(acc[k, 6])
+                recs.append(rec)
             out.append(recs)
         return out
