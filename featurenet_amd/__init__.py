@@ -9,7 +9,8 @@ __version__ = "0.1.0"
 # Public API (``featurenet_amd.api``), resolved lazily so importing the package
 # stays cheap and does not pull in torch-heavy modules until they are used.
 _API = ("train", "classify", "segment", "extract_features", "label_components", "evaluate", "evaluate_segmentation",
-        "evaluate_features", "match_features", "generate_parts", "voxelize", "load", "save", "build_model", "search", "TrainResult")
+        "evaluate_features", "match_features", "generate_parts", "voxelize", "distance_transform", "EDT_INF", "load", "save",
+        "build_model", "search", "TrainResult")
 
 
 def __getattr__(name):

@@ -1,6 +1,6 @@
 """Public Python API: ``train()``, ``classify()``, ``segment()``, ``extract_features()``,
 ``label_components()``, ``evaluate()``, ``evaluate_segmentation()``, ``evaluate_features()``,
-``match_features()``, ``generate_parts()``, ``load()``, ``save()``, ``build_model()`` and ``search()``.
+``match_features()``, ``generate_parts()``, ``voxelize()``, ``distance_transform()``, ``load()``, ``save()``, ``build_model()`` and ``search()``.
 
 Reference parity: the de-facto entry point of the reference is the
 ``TensorflowGenerator(product, epochs, dataset, ...)`` constructor
@@ -31,6 +31,7 @@ from .ir.compile import CandidateNet, compile_model
 from .ir.parse import parse_feature_model
 from .ir.spec import ModelSpec
 from .ir.templates import TEMPLATES
+from .ops.reference import EDT_INF  # noqa: F401
 from .models.featurenet3d import FeatureNet3D, FeatureNet3DConfig, FeatureNet3DSeg
 from .training.callbacks import reference_callbacks
 from .training.checkpoint import read_checkpoint, save_checkpoint
@@ -280,7 +281,7 @@ def evaluate_segmentation(model, x, y, batch_size: int = 32, device=None, packed
 @torch.no_grad()
 def extract_features(model, x, batch_size: int = 32, device=None, packed_size: int | None = None,
                      background: int | None = 0, connectivity: int = 6, min_voxels: int = 1,
-                     return_ids: bool = False, access: bool = False):
+                     return_ids: bool = False, access: bool = False, dimensions: bool = False):
     """The machining features of each part -> (one list of :class:`FeatureInstance` per sample,
     ids int32 [N, S, S, S] or None).
 
@@ -297,6 +298,13 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
     toward ``+x`` when no material (``x != 0``) lies beyond it in its x column, and so on for the
     six faces ``+z, -z, +x, -x, +y, -y`` (``+z`` is the high-index end of z).  The counts are made
     on the model's device (``ops.access``); 8 more integers per component cross to the host.
+
+    With ``dimensions`` every record also says how wide the feature is: ``clearance2`` is the
+    largest squared Euclidean distance from one of its voxels to the nearest material voxel (``x
+    != 0``; the faces of the grid are no wall, so a through hole is measured against its side),
+    ``clearance_at`` the first voxel that attains it, ``wall_voxels`` the voxels with a material
+    face neighbour; ``clearance`` and ``tool_diameter`` follow from these.  The distance transform
+    runs on the model's device (``ops.edt``); 4 more integers per component cross to the host.
     """
     from .utils.seginstances import FeatureInstance
 
@@ -318,9 +326,10 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
         if packed_size is not None:
             xb = unpack_voxels(xb, packed_size)
         xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
-        table, offsets, idb, *acc = model.instances(xb, background=background, connectivity=connectivity,
-                                                    want_ids=return_ids, want_access=access)
-        feats += FeatureInstance.from_table(table, offsets, min_voxels, access=acc[0] if access else None)
+        table, offsets, idb, *more = model.instances(xb, background=background, connectivity=connectivity,
+                                                     want_ids=return_ids, want_access=access, want_dims=dimensions)
+        feats += FeatureInstance.from_table(table, offsets, min_voxels, access=more[0] if access else None,
+                                            dims=more[-1] if dimensions else None, shape=tuple(xb.shape[1:4]))
         if return_ids:
             ids.append(idb.cpu())
     if not return_ids:
@@ -330,7 +339,8 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
 
 
 @torch.no_grad()
-def label_components(labels, background: int | None = 0, connectivity: int = 6, device=None, occupancy=None):
+def label_components(labels, background: int | None = 0, connectivity: int = 6, device=None, occupancy=None,
+                     dimensions: bool = False):
     """Connected components of label volumes the caller already has (ground truth, say) ->
     (ids int32 [N, D, H, W], one list of :class:`FeatureInstance` per sample).
 
@@ -338,10 +348,15 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     0..255; ``background`` and ``connectivity`` as for :func:`extract_features`.  ``device``
     defaults to the GPU when there is one (the ``ccl`` kernels), else the CPU reference path.
     ``occupancy``, an integer or bool array of the labels' shape (material: non-zero), adds the
-    access counts to the records as :func:`extract_features` does with ``access``.
+    access counts to the records as :func:`extract_features` does with ``access``; ``dimensions``
+    (which needs ``occupancy``) adds the clear widths as its ``dimensions`` does.
     """
-    from .ops import access, ccl
+    from .ops import access, ccl, edt
     from .utils.seginstances import FeatureInstance
+
+    if dimensions and occupancy is None:
+        raise ValueError("label_components(): dimensions=True needs occupancy (the material the widths are "
+                         "measured against)")
 
     lt = torch.as_tensor(np.asarray(labels)) if not isinstance(labels, torch.Tensor) else labels
     if lt.is_floating_point() or lt.dtype == torch.bool:
@@ -364,10 +379,37 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     lt = lt.to(device).to(torch.uint8).contiguous()
     roots, flags = ccl.connected_components(lt, background, connectivity, return_flags=True)
     ids, table, offsets = ccl.instance_table(lt, roots, want_ids=True, flags=flags)
-    acc = None
+    acc = dim = None
     if ot is not None:
-        acc, _ = access.access_table(ids, offsets, (ot.to(device) != 0).to(torch.uint8), rows=table.shape[0])
-    return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets, access=acc)
+        occ = (ot.to(device) != 0).to(torch.uint8)
+        acc, _ = access.access_table(ids, offsets, occ, rows=table.shape[0])
+        if dimensions:
+            dim, _ = edt.dimension_table(ids, offsets, occ, rows=table.shape[0])
+    return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets, access=acc, dims=dim,
+                                                         shape=tuple(lt.shape[1:]))
+
+
+@torch.no_grad()
+def distance_transform(volume, border: bool = False, device=None):
+    """Exact squared Euclidean distance transform -> int32 ``[N, D, H, W]`` (or ``[D, H, W]`` for
+    one ``[D, H, W]`` volume): the squared distance, in voxels, from every voxel to the nearest
+    non-zero voxel of ``volume`` (an integer or bool array) of the same sample, 0 on those,
+    :data:`EDT_INF` in a sample that has none.  With ``border`` the positions just outside the
+    grid count as non-zero too.  Each axis is at most 256 long.  ``device`` defaults to the GPU
+    when there is one (the ``edt`` kernels), else the CPU reference path; the result is the same.
+    """
+    from .ops import edt
+
+    vt = torch.as_tensor(np.asarray(volume)) if not isinstance(volume, torch.Tensor) else volume
+    if vt.is_floating_point() or vt.is_complex():
+        raise ValueError(f"distance_transform(): volume must be integers or bools, not {vt.dtype}")
+    if vt.dim() not in (3, 4):
+        raise ValueError(f"distance_transform(): volume must be [D, H, W] or [N, D, H, W], not {tuple(vt.shape)}")
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    seeds = (vt.to(device) != 0).to(torch.uint8)
+    d2 = edt.distance_sq(seeds if vt.dim() == 4 else seeds[None], border=border)
+    return (d2 if vt.dim() == 4 else d2[0]).cpu().numpy()
 
 
 def _label_volumes(labels, what: str, name: str = "labels") -> torch.Tensor:

@@ -246,10 +246,29 @@ def cmd_features(a) -> int:
     feats, ids = api.extract_features(a.model, x, packed_size=a.packed_size,
                                       background=None if a.background < 0 else a.background,
                                       connectivity=a.connectivity, min_voxels=a.min_voxels, return_ids=bool(a.ids),
-                                      access=a.access)
+                                      access=a.access, dimensions=a.dimensions)
     if a.ids:
         np.save(a.ids, ids)
     summary = json.dumps({"samples": [[f.to_dict(a.access_fraction) for f in fs] for fs in feats]})
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(summary + "\n")
+    print(summary)
+    return 0
+
+
+def cmd_distance(a) -> int:
+    import numpy as np
+
+    from . import api
+
+    vol = np.load(a.input, allow_pickle=False)
+    d2 = api.distance_transform(vol, border=a.border, device=a.device or None)
+    np.save(a.output, d2)
+    finite = d2[d2 < api.EDT_INF]
+    summary = json.dumps({"shape": list(d2.shape), "seeds": int((d2 == 0).sum()),
+                          "max_distance_sq": int(finite.max()) if finite.size else None,
+                          "unreached_voxels": int((d2 >= api.EDT_INF).sum())})
     if a.json:
         with open(a.json, "w") as f:
             f.write(summary + "\n")
@@ -507,7 +526,18 @@ def build_parser() -> argparse.ArgumentParser:
                          "through, enclosed")
     ft.add_argument("--access-fraction", type=float, default=1.0, metavar="F",
                     help="with --access: a face is open when at least this fraction of the voxels is (default 1.0)")
+    ft.add_argument("--dimensions", action="store_true",
+                    help="add the clear widths: clearance2 (largest squared distance to the material), clearance_at, "
+                         "tool_diameter, wall_voxels")
     ft.set_defaults(fn=cmd_features)
+
+    dt = sub.add_parser("distance", help="exact squared Euclidean distance to the nearest non-zero voxel -> int32 .npy")
+    dt.add_argument("input", help="[D, H, W] or [N, D, H, W] integer or bool array (.npy), each axis at most 256")
+    dt.add_argument("-o", "--output", required=True, help="squared distances, int32, the input's shape (.npy)")
+    dt.add_argument("--border", action="store_true", help="the positions just outside the grid count as non-zero too")
+    dt.add_argument("--device", default="", help="cuda / cpu (default: the GPU when there is one)")
+    dt.add_argument("--json", default="", metavar="OUT", help="also write the summary to this file")
+    dt.set_defaults(fn=cmd_distance)
 
     sf = sub.add_parser("score-features", help="match the predicted feature instances of a segmentation checkpoint "
                                                "to the true ones: per-class TP / FP / FN, F1, panoptic quality")

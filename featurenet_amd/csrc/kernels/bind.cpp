@@ -56,6 +56,9 @@ void fn_access_chunk(int*);
 int fn_access_extents(const void*, void*, void*, void*, int, int, int, int, hipStream_t);
 int fn_access_stats(const void*, const void*, const void*, const void*, const void*, void*, void*, int, int, int, int,
                     long long, hipStream_t);
+void fn_edt_chunk(int*);
+int fn_edt_transform(const void*, void*, void*, int, int, int, int, int, int, hipStream_t);
+int fn_edt_stats(const void*, const void*, const void*, void*, int, int, int, int, long long, hipStream_t);
 int fn_pw_wgrad(const void*, const void*, float*, long long, int, int, hipStream_t, const float*, const float*, int,
                 float*);
 int fn_pw_wgrad_blocks(long long, int, int);
@@ -782,6 +785,38 @@ PYBIND11_MODULE(_C, m) {
         "access_stats");
   }, py::arg("ids"), py::arg("offsets"), py::arg("ex"), py::arg("ey"), py::arg("ez"), py::arg("mask"), py::arg("acc"),
      py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("T"), py::arg("st"), py::arg("ext"));
+  // dimensions of feature instances (edt.hip): seeds uint8 [N][D][H][W] (a seed: != 0; border: every position just
+  // outside the grid is one too), D, H, W <= 256; t and d2 int32 [N][D][H][W], which may be one buffer: passes bit 0
+  // writes t (the squared distance within the voxel's plane), bit 1 d2 from t (the squared distance, 1 << 30 where
+  // the sample has no seed); ext = {numel(seeds), numel(t), numel(d2)}
+  m.def("edt_chunk", []() {
+    int t[2];
+    fn_edt_chunk(t);
+    return py::make_tuple(t[0], t[1]);
+  });
+  m.def("edt_transform", [](uintptr_t seeds, uintptr_t t, uintptr_t d2, int N, int D, int H, int W, bool border,
+                            int passes, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "edt_transform", "seeds");
+    fits(ext, 1, prod({N, D, H, W}), "edt_transform", "t");
+    fits(ext, 2, prod({N, D, H, W}), "edt_transform", "d2");
+    chk(fn_edt_transform(P<const void*>(seeds), P<void*>(t), P<void*>(d2), N, D, H, W, border, passes, S(st)),
+        "edt_transform");
+  }, py::arg("seeds"), py::arg("t"), py::arg("d2"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"),
+     py::arg("border"), py::arg("passes"), py::arg("st"), py::arg("ext"));
+  // ids int32 [N*V] and offsets int64 [N+1] as for access_stats, d2 int32 [N*V]; raw int64 [T][3] (fully rewritten):
+  // the largest d2 << 32 | (0xFFFFFFFF - index in the sample) over the row's voxels, its voxels with d2 == 1, its
+  // voxels (all 0: no voxel carries the row); ext = {numel(ids), numel(offsets), numel(d2), numel(raw)}
+  m.def("edt_stats", [](uintptr_t ids, uintptr_t offsets, uintptr_t d2, uintptr_t raw, int N, int D, int H, int W,
+                        long long T, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "edt_stats", "ids");
+    fits(ext, 1, N < 0 ? -1 : N + 1LL, "edt_stats", "offsets");
+    fits(ext, 2, prod({N, D, H, W}), "edt_stats", "d2");
+    fits(ext, 3, prod({T, 3}), "edt_stats", "raw");
+    chk(fn_edt_stats(P<const void*>(ids), P<const void*>(offsets), P<const void*>(d2), P<void*>(raw), N, D, H, W, T,
+                     S(st)),
+        "edt_stats");
+  }, py::arg("ids"), py::arg("offsets"), py::arg("d2"), py::arg("raw"), py::arg("N"), py::arg("D"), py::arg("H"),
+     py::arg("W"), py::arg("T"), py::arg("st"), py::arg("ext"));
   // multi-feature parts from their parameter tables (partgen.hip): params int32 [N][K][16]; occ / labels / slots
   // uint8 [N][S][S][S] (8-byte aligned) and packed uint8 [N][S^3/8], each 0 = not wanted; S % 8 == 0, 8 <= S <=
   // 256, K <= 32; ext = {numel(params), numel(occ), numel(packed), numel(labels), numel(slots)}

@@ -260,7 +260,7 @@ class FeatureNet3DSeg(nn.Module):
 
     @torch.no_grad()
     def instances(self, x: torch.Tensor, background: int | None = 0, connectivity: int = 6,
-                  want_ids: bool = False, want_access: bool = False):
+                  want_ids: bool = False, want_access: bool = False, want_dims: bool = False):
         """The features in each sample: :meth:`predict`'s labels split into connected components
         -> ``(table, offsets, ids or None)`` on the model's device.  ``table`` int64 ``[T, 13]``
         has one row per component (``sample, class, voxels, root, z0, y0, x0, z1, y1, x1, sum_z,
@@ -272,21 +272,32 @@ class FeatureNet3DSeg(nn.Module):
         With ``want_access`` -> ``(table, offsets, ids or None, acc)``: ``acc`` int64 ``[T, 8]``
         counts, row by row of ``table``, the component's voxels that are open toward the faces
         ``+z, -z, +x, -x, +y, -y`` of the grid (no material, ``x != 0``, lies beyond the voxel on
-        that side), toward none, and all of them (``ops.access``)."""
-        from ..ops import access, ccl
+        that side), toward none, and all of them (``ops.access``).
+
+        With ``want_dims`` ``dim`` int64 ``[T, 4]`` is appended (after ``acc`` when that is there):
+        row by row of ``table`` the largest squared distance from one of the component's voxels
+        to the material, the smallest index ``(z * S + y) * S + x`` of a voxel that attains it,
+        the component's voxels with a material face neighbour, and all of them (``ops.edt``)."""
+        from ..ops import access, ccl, edt
 
         if connectivity not in (6, 26):
             raise ValueError(f"instances: connectivity must be 6 or 26, not {connectivity!r}")
         labels = self.predict(x)
         roots, flags = ccl.connected_components(labels, background, connectivity, return_flags=True)
-        ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids or want_access, flags=flags)
-        if not want_access:
+        ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids or want_access or want_dims,
+                                                 flags=flags)
+        if not (want_access or want_dims):
             return table, offsets, ids
         occ = (x != 0).to(device=labels.device, dtype=torch.uint8)
         if occ.dim() == 5:                       # [N, S, S, S, C]: material in any channel
             occ = occ.amax(-1)
-        acc, _ = access.access_table(ids, offsets, occ.reshape(labels.shape), rows=table.shape[0])
-        return table, offsets, ids if want_ids else None, acc
+        occ = occ.reshape(labels.shape)
+        out = [table, offsets, ids if want_ids else None]
+        if want_access:
+            out.append(access.access_table(ids, offsets, occ, rows=table.shape[0])[0])
+        if want_dims:
+            out.append(edt.dimension_table(ids, offsets, occ, rows=table.shape[0])[0])
+        return tuple(out)
 
     def match(self, x: torch.Tensor, y: torch.Tensor, background: int | None = 0, connectivity: int = 6):
         """The predicted features against the true ones: the instances of :meth:`predict`'s labels,

@@ -312,6 +312,68 @@ def access_table(ids: torch.Tensor, offsets: torch.Tensor, occ: torch.Tensor, wa
     return acc, (mask.to(torch.uint8) if want_mask else None)
 
 
+EDT_INF = 1 << 30          # distance_sq of a sample without a seed
+EDT_MAX_S = 256            # longest axis distance_sq takes: every result fits 3 * 255^2
+
+
+def distance_sq(seeds: torch.Tensor, border: bool = False) -> torch.Tensor:
+    """Exact squared Euclidean distance transform of ``seeds`` uint8 ``[N, D, H, W]`` (a voxel is a
+    seed when ``seeds != 0``) -> int32 ``[N, D, H, W]``: the smallest ``(z-z')^2 + (y-y')^2 +
+    (x-x')^2`` over the seeds ``(z', y', x')`` of the same sample, 0 on a seed, ``EDT_INF`` in a
+    sample without one.  With ``border`` every position just outside the grid (index -1 or the
+    axis length, on any axis) is a seed too, so the result is also bounded by the smallest ``min(i
+    + 1, L - i)^2`` over the axes.  Each axis is at most ``EDT_MAX_S``.
+
+    Three separable min-plus passes (x, y, z), ``out[i] = min_j g[j] + (i - j)^2`` from ``g = 0`` on
+    seeds and ``EDT_INF`` elsewhere, in int64: the oracle of ``edt_xy`` / ``edt_z`` and the CPU path
+    of ``ops.edt.distance_sq``."""
+    if seeds.dim() != 4 or seeds.dtype != torch.uint8:
+        raise ValueError(f"distance_sq: seeds must be uint8 [N, D, H, W], not {seeds.dtype} {tuple(seeds.shape)}")
+    if max(seeds.shape[1:]) > EDT_MAX_S:
+        raise ValueError(f"distance_sq: each of D, H, W is at most {EDT_MAX_S}, not {tuple(seeds.shape[1:])}")
+    inf = torch.tensor(EDT_INF, dtype=torch.int64, device=seeds.device)
+    g = torch.where(seeds != 0, 0, inf)
+    if g.numel() == 0:
+        return g.to(torch.int32)
+    for axis in (3, 2, 1):
+        L = seeds.shape[axis]
+        i = torch.arange(L, device=seeds.device).view([L if a == axis else 1 for a in range(4)])
+        out = torch.minimum((i + 1) ** 2, (L - i) ** 2).expand(g.shape).clone() if border else g.clone()
+        for j in range(L):
+            out = torch.minimum(out, g.narrow(axis, j, 1) + (i - j) ** 2)
+        g = out.clamp_(max=EDT_INF)
+    return g.to(torch.int32)
+
+
+def dimension_table(ids: torch.Tensor, offsets: torch.Tensor, d2: torch.Tensor) -> torch.Tensor:
+    """Dimension table of an instance-id volume over a squared-distance volume -> int64 ``[T, 4]``.
+
+    ``ids`` int32 ``[N, D, H, W]`` and ``offsets`` int64 ``[N + 1]`` as :func:`instance_table` gives
+    them (``T = offsets[-1]``), ``d2`` int32 of the ids' shape (:func:`distance_sq`).  Row ``offsets[n]
+    + id - 1`` holds, of id ``id`` of sample ``n``: ``r2``, the largest ``d2`` over its voxels; ``at``,
+    the smallest linear index ``(z * H + y) * W + x`` within the sample of a voxel that attains it;
+    ``wall``, its voxels with ``d2 == 1``; ``voxels``, all of them.  A row that no voxel carries
+    holds ``(-1, -1, 0, 0)``; a voxel with id 0 or whose row lies outside the table counts nowhere.
+    Exact integers: the oracle of ``edt_stats`` and the CPU path of ``ops.edt.dimension_table``."""
+    N, D, H, W = ids.shape
+    dev = ids.device
+    T = int(offsets[-1])
+    row = ids.to(torch.int64) + offsets.to(torch.int64)[:-1].view(N, 1, 1, 1) - 1
+    fg = (ids > 0) & (row >= 0) & (row < T)
+    dim = torch.zeros(T, 4, dtype=torch.int64, device=dev)
+    if T:
+        rows, d = row[fg], d2.to(torch.int64)[fg]
+        lin = torch.arange(D * H * W, device=dev).view(1, D, H, W).expand(ids.shape)[fg]
+        # the largest d2 and, among equals, the smallest index: one max over (d2, ~index)
+        key = torch.full((T,), -1, dtype=torch.int64, device=dev).scatter_reduce(
+            0, rows, d << 32 | (0xFFFFFFFF - lin), "amax")
+        dim[:, 0] = torch.where(key >= 0, key >> 32, -1)
+        dim[:, 1] = torch.where(key >= 0, 0xFFFFFFFF - (key & 0xFFFFFFFF), -1)
+        dim[:, 2] = torch.bincount(rows[d == 1], minlength=T)
+        dim[:, 3] = torch.bincount(rows, minlength=T)
+    return dim
+
+
 def _part_volume(cls: int, f: dict, X, Y, Z, top: int):
     """The volume of one feature class over canonical quarter-voxel coordinates ``X, Y, Z``
     (int64 ``[n, S, S, S]``); ``f`` maps the field names of a table row to ``[n, 1, 1, 1]``."""

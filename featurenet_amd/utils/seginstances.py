@@ -2,13 +2,17 @@
 
 One :class:`FeatureInstance` per row of the instance table (``ops.ccl.instance_table``): exact
 integer counts and bounds, the centroid as ``sum / voxels`` in float64 on the host; with an access
-table (``ops.access.access_table``) also the voxels open toward each face of the grid.
+table (``ops.access.access_table``) also the voxels open toward each face of the grid; with a dimension table (``ops.edt.dimension_table``) also its clear width: the
+largest squared distance from one of its voxels to the material, and where that voxel lies.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass
 
 import numpy as np
+
+from ..ops.reference import EDT_INF
 
 from .partfeatures import FACES
 
@@ -25,6 +29,24 @@ class FeatureInstance:
     centroid: tuple          # (z, y, x), float64
     access: tuple | None = None    # its voxels open toward each face, in FACES order (None: not computed)
     enclosed: int | None = None    # its voxels open toward no face
+    clearance2: int | None = None  # the largest squared distance from a voxel's centre to a material voxel's
+    clearance_at: tuple | None = None   # (z, y, x) of the first voxel, in raster order, that attains it
+    wall_voxels: int | None = None      # its voxels with a material face neighbour
+
+    @property
+    def clearance(self) -> float | None:
+        """The distance from the deepest voxel's centre to the nearest material voxel's centre, in
+        voxels (``inf`` in a part without material); None without dimensions."""
+        if self.clearance2 is None:
+            return None
+        return math.inf if self.clearance2 >= EDT_INF else math.sqrt(self.clearance2)
+
+    @property
+    def tool_diameter(self) -> float | None:
+        """The diameter in voxels of the largest ball, centred on a voxel centre, that touches no
+        material voxel: ``max(0, 2 * clearance - 1)``; None without dimensions."""
+        c = self.clearance
+        return None if c is None else max(0.0, 2.0 * c - 1.0)
 
     def open_faces(self, min_fraction: float = 1.0) -> tuple:
         """The names of the faces toward which at least ``min_fraction`` of the voxels are open:
@@ -48,20 +70,27 @@ class FeatureInstance:
 
     def to_dict(self, min_fraction: float = 1.0) -> dict:
         """JSON-safe record; with access counts also ``access`` (face -> voxels), ``open_faces``
-        (at ``min_fraction``), ``through`` and ``enclosed``."""
+        (at ``min_fraction``), ``through`` and ``enclosed``; with dimensions also ``clearance2``,
+        ``clearance_at``, ``tool_diameter`` (None where it is unbounded) and ``wall_voxels``."""
         d = {"id": self.id, "class": self.cls, "voxels": self.voxels, "bbox": list(self.bbox),
              "centroid": list(self.centroid)}
         if self.access is not None:
             d.update(access=dict(zip(FACES, self.access)), open_faces=list(self.open_faces(min_fraction)),
                      through=self.through, enclosed=self.enclosed)
+        if self.clearance2 is not None:
+            tool = self.tool_diameter
+            d.update(clearance2=self.clearance2, clearance_at=list(self.clearance_at),
+                     tool_diameter=tool if math.isfinite(tool) else None, wall_voxels=self.wall_voxels)
         return d
 
     @staticmethod
-    def from_table(table, offsets, min_voxels: int = 1, access=None) -> "list[list[FeatureInstance]]":
+    def from_table(table, offsets, min_voxels: int = 1, access=None, dims=None,
+                   shape=None) -> "list[list[FeatureInstance]]":
         """Per-sample record lists from an instance table int64 ``[T, 13]`` and its ``offsets``
         ``[N + 1]`` (tensors or arrays).  Components of fewer than ``min_voxels`` voxels are left
         out; the others keep their ``id``.  ``access``: the access table int64 ``[T, 8]`` of the
-        same rows, or None."""
+        same rows, or None.  ``dims``: the dimension table int64 ``[T, 4]`` of the same rows, or None;
+        with it ``shape``, the ``(D, H, W)`` of a sample, which turns ``at`` into ``(z, y, x)``."""
         tab = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.int64).reshape(-1, 13)
         off = np.asarray(offsets.cpu() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
         acc = None
@@ -69,6 +98,14 @@ class FeatureInstance:
             acc = np.asarray(access.cpu() if hasattr(access, "cpu") else access, dtype=np.int64).reshape(-1, 8)
             if len(acc) != len(tab) or not np.array_equal(acc[:, 7], tab[:, 2]):
                 raise ValueError("from_table: the access table does not belong to this instance table")
+        dim = None
+        if dims is not None:
+            dim = np.asarray(dims.cpu() if hasattr(dims, "cpu") else dims, dtype=np.int64).reshape(-1, 4)
+            if len(dim) != len(tab) or not np.array_equal(dim[:, 3], tab[:, 2]):
+                raise ValueError("from_table: the dimension table does not belong to this instance table")
+            if shape is None or len(shape) != 3:
+                raise ValueError("from_table: dims needs shape = (D, H, W)")
+            _, H, W = (int(s) for s in shape)
         out = []
         for n in range(len(off) - 1):
             recs = []
@@ -83,6 +120,10 @@ class FeatureInstance:
                                       centroid=tuple(float(c) for c in cen))
                 if acc is not None:
                     rec.access, rec.enclosed = tuple(int(c) for c in acc[k, :6]), int(acc[k, 6])
+                if dim is not None:
+                    r2, at, wall = (int(v) for v in dim[k, :3])
+                    rec.clearance2, rec.wall_voxels = r2, wall
+                    rec.clearance_at = (at // (H * W), at // W % H, at % W)
                 recs.append(rec)
             out.append(recs)
         return out
