@@ -12,16 +12,11 @@
 //                             int64 [T][8], one row per row of the instance table: voxels open toward
 //                             each face, voxels open toward none, voxels
 // Every result is an integer that does not depend on the order of the atomics.
-#include "common.h"
+#include "instance_pass.h"
 
-constexpr int ACC_NTHR = 256;
+constexpr int ACC_NTHR = 256;                   // the extents kernel
 constexpr int ACC_NWAVE = ACC_NTHR / FN_WAVE;
 constexpr int ACC_NCOL = 8;                     // +z -z +x -x +y -y none voxels
-constexpr int ACC_SLOTS = 512;                  // LDS run table, direct-mapped by table row
-constexpr int ACC_CHUNK = 16 * ACC_NTHR;        // voxels per workgroup
-static_assert((ACC_SLOTS & (ACC_SLOTS - 1)) == 0 && ACC_NTHR % FN_WAVE == 0, "table shape");
-
-#define ACC_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // ---------------------------------------------------------------------------------------------
 // Column extents
@@ -89,75 +84,48 @@ __global__ __launch_bounds__(ACC_NTHR) void access_init_kernel(long long* __rest
   if (i < T * ACC_NCOL) acc[i] = 0;
 }
 
-// g / d for 0 <= g < 2^31 and d >= 1 from r = acc_recip(d) = floor(2^32 / d) (d >= 2): the high word
-// of g * r is the quotient or one less (g * (2^32 - d*r) / (d * 2^32) < g / 2^32 < 1), which the
-// remainder tells.  The kernel below divides every voxel's index three times; as plain divisions
-// those were most of its instructions.
-static unsigned acc_recip(int d) { return d >= 2 ? (unsigned)((1ull << 32) / (unsigned)d) : 0u; }
-__device__ __forceinline__ int acc_div(int g, int d, unsigned r) {
-  const unsigned q = d == 1 ? (unsigned)g : __umulhi((unsigned)g, r);
-  return (int)(q + ((unsigned)g - q * (unsigned)d >= (unsigned)d));
-}
-
-// One lane per voxel, ACC_CHUNK consecutive voxels (of the flat [N*V] range, < 2^31) per workgroup,
-// as ccl_stats_kernel.  ids int32 [N*V]: per-sample ids from 1, 0 = none; offsets int64 [N+1]: the
-// rows of each sample, so a voxel with id > 0 counts in the 1-based row offsets[n] + id (a row
-// outside [1, T] counts nowhere).  A run of one row number along a row of W (it breaks at lane 0,
-// at x == 0 and where the row number changes) is one update, made by its first lane: the x counts
-// from the run's ends and the row's extents, the others as popcounts of the bits' ballots under the
-// run's lanes.  The updates of a workgroup meet in an LDS table of ACC_SLOTS rows first (a slot held
-// by another row sends the update to global memory directly); each occupied slot then adds its
-// non-zero counters to acc.  mask uint8 [N*V] or null: the six bits of every voxel, 0 where it
-// counts nowhere.
-__global__ __launch_bounds__(ACC_NTHR) void access_stats_kernel(const int* __restrict__ ids,
-                                                                const long long* __restrict__ offsets,
-                                                                const int2* __restrict__ ex,
-                                                                const int2* __restrict__ ey,
-                                                                const int2* __restrict__ ez,
-                                                                uint8_t* __restrict__ mask, long long* acc, int total,
-                                                                int V, int D, int H, int W, int T, unsigned rV,
-                                                                unsigned rH, unsigned rW) {
-  __shared__ int s_gid[ACC_SLOTS];
-  __shared__ unsigned s_cnt[ACC_SLOTS][ACC_NCOL];
-  const int tid = threadIdx.x, lane = tid & 63;
-  for (int s = tid; s < ACC_SLOTS; s += ACC_NTHR) {
+// The instance pass of instance_pass.h.  ids int32 [N*V]: per-sample ids from 1, 0 = none; offsets
+// int64 [N+1]: the rows of each sample (ip_row).  A run of one row number along a row of W takes its
+// x counts from the run's ends and the row's extents, the others as popcounts of the bits' ballots
+// under the run's lanes; each occupied slot adds its non-zero counters to acc.  mask uint8 [N*V] or
+// null: the six bits of every voxel, 0 where it counts nowhere.
+__global__ __launch_bounds__(IP_NTHR) void access_stats_kernel(const int* __restrict__ ids,
+                                                              const long long* __restrict__ offsets,
+                                                              const int2* __restrict__ ex,
+                                                              const int2* __restrict__ ey,
+                                                              const int2* __restrict__ ez, uint8_t* __restrict__ mask,
+                                                              long long* acc, int total, int V, int D, int H, int W,
+                                                              int T, unsigned rV, unsigned rH, unsigned rW) {
+  __shared__ int s_gid[IP_SLOTS];
+  __shared__ unsigned s_cnt[IP_SLOTS][ACC_NCOL];
+  const int tid = threadIdx.x;
+  for (int s = tid; s < IP_SLOTS; s += IP_NTHR) {
     s_gid[s] = 0;
 #pragma unroll
     for (int k = 0; k < ACC_NCOL; ++k) s_cnt[s][k] = 0;
   }
   __syncthreads();
-  const int g0 = blockIdx.x * ACC_CHUNK;        // (total < 2^31 and the grid covers it: no overflow below)
-  for (int it = 0; it < ACC_CHUNK / ACC_NTHR; ++it) {
-    const unsigned gu = (unsigned)g0 + (unsigned)(it * ACC_NTHR + tid);
-    const bool valid = gu < (unsigned)total;
-    const int g = valid ? (int)gu : total - 1;
-    const int n = acc_div(g, V, rV), zy = acc_div(g, W, rW), x = g - zy * W;    // zy = (n*D + z)*H + y
-    const int nz = acc_div(zy, H, rH), y = zy - nz * H, z = nz - n * D;         // nz = n*D + z
-    const int id = ids[g];
-    const long long row = offsets[n] + id;
-    const bool on = valid && id > 0 && row >= 1 && row <= T;
-    const int gid = on ? (int)row : 0;
+  for (int it = 0; it < IP_CHUNK / IP_NTHR; ++it) {
+    const auto [g, valid] = ip_voxel(it, total);
+    const int n = ip_div(g, V, rV), zy = ip_div(g, W, rW), x = g - zy * W;      // zy = (n*D + z)*H + y
+    const int nz = ip_div(zy, H, rH), y = zy - nz * H, z = nz - n * D;          // nz = n*D + z
+    const int gid = ip_row(offsets, n, ids[g], valid, T);
     const int2 cx = ex[zy], cy = ey[(long long)nz * W + x], cz = ez[(long long)(n * H + y) * W + x];
     const bool pz = cz.y <= z, mz = cz.x >= z, px = cx.y <= x, mx = cx.x >= x, py = cy.y <= y, my = cy.x >= y;
     const unsigned bits = pz | mz << 1 | px << 2 | mx << 3 | py << 4 | my << 5;
-    if (mask && valid) mask[g] = on ? (uint8_t)bits : (uint8_t)0;
+    if (mask && valid) mask[g] = gid > 0 ? (uint8_t)bits : (uint8_t)0;
     const unsigned long long b_pz = __ballot(pz), b_mz = __ballot(mz), b_py = __ballot(py), b_my = __ballot(my),
                              b_none = __ballot(bits == 0);
-    const int prev = __shfl_up(gid, 1, 64);
-    const unsigned long long heads = __ballot(lane == 0 || x == 0 || gid != prev);
-    const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
-    const int len = (above ? __builtin_ctzll(above) : 64) - lane;
-    if (((heads >> lane) & 1) && gid > 0) {
-      const unsigned long long run = (len == 64 ? ~0ull : (1ull << len) - 1) << lane;
+    const auto [head, len, run] = ip_run(gid, x == 0);
+    if (head && gid > 0) {
       const int x1 = x + len - 1;                // the run is x .. x1 of one row: one (lo, hi) for all of it
       unsigned c[ACC_NCOL];
       c[0] = __popcll(b_pz & run), c[1] = __popcll(b_mz & run);
       c[2] = (unsigned)max(0, x1 - max(x, cx.y) + 1), c[3] = (unsigned)max(0, min(x1, cx.x) - x + 1);
       c[4] = __popcll(b_py & run), c[5] = __popcll(b_my & run);
       c[6] = __popcll(b_none & run), c[7] = (unsigned)len;
-      const int slot = gid & (ACC_SLOTS - 1);
-      const int held = atomicCAS(&s_gid[slot], 0, gid);
-      if (held == 0 || held == gid) {
+      const int slot = ip_claim(s_gid, gid);
+      if (slot >= 0) {
 #pragma unroll
         for (int k = 0; k < ACC_NCOL; ++k)
           if (c[k]) atomicAdd(&s_cnt[slot][k], c[k]);
@@ -165,16 +133,16 @@ __global__ __launch_bounds__(ACC_NTHR) void access_stats_kernel(const int* __res
         long long* dst = acc + (long long)(gid - 1) * ACC_NCOL;
 #pragma unroll
         for (int k = 0; k < ACC_NCOL; ++k)
-          if (c[k]) __hip_atomic_fetch_add(&dst[k], (long long)c[k], ACC_RLX_AGENT);
+          if (c[k]) __hip_atomic_fetch_add(&dst[k], (long long)c[k], IP_RLX_AGENT);
       }
     }
   }
   __syncthreads();
-  for (int i = tid; i < ACC_SLOTS * ACC_NCOL; i += ACC_NTHR) {
+  for (int i = tid; i < IP_SLOTS * ACC_NCOL; i += IP_NTHR) {
     const int s = i / ACC_NCOL, k = i % ACC_NCOL, gid = s_gid[s];
     const unsigned cnt = s_cnt[s][k];
     if (gid > 0 && cnt)
-      __hip_atomic_fetch_add(&acc[(long long)(gid - 1) * ACC_NCOL + k], (long long)cnt, ACC_RLX_AGENT);
+      __hip_atomic_fetch_add(&acc[(long long)(gid - 1) * ACC_NCOL + k], (long long)cnt, IP_RLX_AGENT);
   }
 }
 
@@ -182,19 +150,13 @@ __global__ __launch_bounds__(ACC_NTHR) void access_stats_kernel(const int* __res
 // Entry points
 // ---------------------------------------------------------------------------------------------
 
-static bool acc_shape_ok(int N, int D, int H, int W) {
-  if (N < 1 || D < 1 || H < 1 || W < 1) return false;
-  const long long V = (long long)D * H * W;
-  return V < (1LL << 31) && V * N < (1LL << 31);
-}
-
-extern "C" void fn_access_chunk(int* t) { t[0] = ACC_CHUNK, t[1] = ACC_SLOTS; }
+extern "C" void fn_access_chunk(int* t) { t[0] = IP_CHUNK, t[1] = IP_SLOTS; }
 
 // occ uint8 [N][D][H][W]; ex int32 [N][D][H][2], ey [N][D][W][2], ez [N][H][W][2] (8-byte aligned), all
 // three written in full.
 extern "C" int fn_access_extents(const void* occ, void* ex, void* ey, void* ez, int N, int D, int H, int W,
                                  hipStream_t st) {
-  if (!acc_shape_ok(N, D, H, W) || !occ || !ex || !ey || !ez) return -2;
+  if (!ip_shape_ok(N, D, H, W) || !occ || !ex || !ey || !ez) return -2;
   if (((uintptr_t)ex | (uintptr_t)ey | (uintptr_t)ez) % 8 != 0) return -2;
   const long long nblk = (long long)N * D + (long long)N * H;   // (< 2^32: N*D*H < 2^31)
   if (nblk >= (1LL << 31)) return -2;
@@ -208,7 +170,7 @@ extern "C" int fn_access_extents(const void* occ, void* ex, void* ey, void* ez, 
 // or null; acc int64 [T][8], fully rewritten.
 extern "C" int fn_access_stats(const void* ids, const void* offsets, const void* ex, const void* ey, const void* ez,
                                void* mask, void* acc, int N, int D, int H, int W, long long T, hipStream_t st) {
-  if (!acc_shape_ok(N, D, H, W) || !ids || !offsets || !ex || !ey || !ez) return -2;
+  if (!ip_shape_ok(N, D, H, W) || !ids || !offsets || !ex || !ey || !ez) return -2;
   if (((uintptr_t)ex | (uintptr_t)ey | (uintptr_t)ez) % 8 != 0) return -2;
   const long long V = (long long)D * H * W, total = V * N;
   if (T < 0 || T > total || (T > 0 && !acc)) return -2;
@@ -217,10 +179,10 @@ extern "C" int fn_access_stats(const void* ids, const void* offsets, const void*
                        0, st, (long long*)acc, T);
     FN_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(access_stats_kernel, dim3((unsigned)((total + ACC_CHUNK - 1) / ACC_CHUNK)), dim3(ACC_NTHR), 0, st,
+  hipLaunchKernelGGL(access_stats_kernel, dim3((unsigned)((total + IP_CHUNK - 1) / IP_CHUNK)), dim3(IP_NTHR), 0, st,
                      (const int*)ids, (const long long*)offsets, (const int2*)ex, (const int2*)ey, (const int2*)ez,
-                     (uint8_t*)mask, (long long*)acc, (int)total, (int)V, D, H, W, (int)T, acc_recip((int)V),
-                     acc_recip(H), acc_recip(W));
+                     (uint8_t*)mask, (long long*)acc, (int)total, (int)V, D, H, W, (int)T, ip_recip((int)V),
+                     ip_recip(H), ip_recip(W));
   FN_CHECK_LAUNCH();
   return 0;
 }

@@ -13,7 +13,7 @@
 //   5  ccl_stats_kernel    dense ids + the table: runs of one component along W are combined in
 //                          the wave (ballot), then in an LDS run table, then added to the table
 // Every result is an integer that does not depend on the order of the merges or of the atomics.
-#include "common.h"
+#include "instance_pass.h"
 
 constexpr int CCL_TD = 8, CCL_TH = 8, CCL_TW = 64;      // tile: 4096 voxels, one wave lane per x
 constexpr int CCL_TV = CCL_TD * CCL_TH * CCL_TW;
@@ -248,8 +248,6 @@ __global__ __launch_bounds__(CCL_NTHR) void ccl_flatten_kernel(int* roots, int* 
 // ---------------------------------------------------------------------------------------------
 
 constexpr int CCL_NCOL = 13;                    // sample class voxels root z0 y0 x0 z1 y1 x1 sum_z sum_y sum_x
-constexpr int CCL_SLOTS = 512;                  // LDS run table, direct-mapped by table row
-constexpr int CCL_CHUNK = 16 * CCL_NTHR;        // voxels per workgroup
 
 __global__ __launch_bounds__(CCL_NTHR) void ccl_table_init_kernel(long long* __restrict__ table, long long T) {
   const long long i = (long long)blockIdx.x * CCL_NTHR + threadIdx.x;
@@ -272,22 +270,20 @@ __device__ __forceinline__ void ccl_row_add(long long* row, long long cnt, int z
   __hip_atomic_fetch_add(&row[12], sx, CCL_RLX_AGENT);
 }
 
-// One lane per voxel, CCL_CHUNK consecutive voxels (of the flat [N*V] range, < 2^31) per
-// workgroup.  rank[g]: inclusive prefix sum of the root flags = 1-based table row of root g.
-// A run of one component along a row of W is one table update, made by its first lane from the
-// run's length alone; the updates of a workgroup meet in an LDS table of CCL_SLOTS rows first
-// (a row held by another component sends the update to global memory directly), so a large
-// component issues one set of global atomics per workgroup, not per voxel.
-__global__ __launch_bounds__(CCL_NTHR) void ccl_stats_kernel(const uint8_t* __restrict__ labels,
-                                                             const int* __restrict__ roots,
-                                                             const int* __restrict__ rank, int* __restrict__ ids,
-                                                             long long* __restrict__ table, int total, int V, int H,
-                                                             int W, int T) {
-  __shared__ int s_gid[CCL_SLOTS];
-  __shared__ int s_mm[CCL_SLOTS][6];
-  __shared__ unsigned long long s_sum[CCL_SLOTS][4];
-  const int tid = threadIdx.x, lane = tid & 63;
-  for (int s = tid; s < CCL_SLOTS; s += CCL_NTHR) {
+// The instance pass of instance_pass.h.  rank[g]: inclusive prefix sum of the root flags = 1-based
+// table row of root g, so a voxel's row is rank[its root], checked against [1, T].  A run of one
+// component along a row of W is one table update from the run's start and length alone, so a
+// large component issues one set of global atomics per workgroup, not per voxel.
+__global__ __launch_bounds__(IP_NTHR) void ccl_stats_kernel(const uint8_t* __restrict__ labels,
+                                                            const int* __restrict__ roots,
+                                                            const int* __restrict__ rank, int* __restrict__ ids,
+                                                            long long* __restrict__ table, int total, int V, int H,
+                                                            int W, int T, unsigned rV, unsigned rH, unsigned rW) {
+  __shared__ int s_gid[IP_SLOTS];
+  __shared__ int s_mm[IP_SLOTS][6];
+  __shared__ unsigned long long s_sum[IP_SLOTS][4];
+  const int tid = threadIdx.x;
+  for (int s = tid; s < IP_SLOTS; s += IP_NTHR) {
     s_gid[s] = 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) s_mm[s][k] = 0x7fffffff, s_mm[s][3 + k] = -1;
@@ -295,13 +291,10 @@ __global__ __launch_bounds__(CCL_NTHR) void ccl_stats_kernel(const uint8_t* __re
     for (int k = 0; k < 4; ++k) s_sum[s][k] = 0;
   }
   __syncthreads();
-  const int g0 = blockIdx.x * CCL_CHUNK;        // (total < 2^31 and the grid covers it: no overflow below)
-  for (int it = 0; it < CCL_CHUNK / CCL_NTHR; ++it) {
-    const unsigned gu = (unsigned)g0 + (unsigned)(it * CCL_NTHR + tid);
-    const bool valid = gu < (unsigned)total;
-    const int g = valid ? (int)gu : total - 1;
-    const int n = g / V, v = g - n * V;
-    const int x = v % W, zy = v / W, y = zy % H, z = zy / H;
+  for (int it = 0; it < IP_CHUNK / IP_NTHR; ++it) {
+    const auto [g, valid] = ip_voxel(it, total);
+    const int n = ip_div(g, V, rV), v = g - n * V;
+    const int zy = ip_div(v, W, rW), x = v - zy * W, z = ip_div(zy, H, rH), y = zy - z * H;
     const int r = roots[g];
     const bool fg = valid && r > 0 && r <= V;
     const int gid0 = rank[fg ? n * V + r - 1 : g];
@@ -313,15 +306,11 @@ __global__ __launch_bounds__(CCL_NTHR) void ccl_stats_kernel(const uint8_t* __re
       long long* row = table + (long long)(gid - 1) * CCL_NCOL;
       row[0] = n, row[1] = labels[g], row[3] = r;
     }
-    const int prev = __shfl_up(gid, 1, 64);
-    const unsigned long long heads = __ballot(lane == 0 || x == 0 || gid != prev);
-    const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
-    const int len = (above ? __builtin_ctzll(above) : 64) - lane;
-    if (((heads >> lane) & 1) && gid > 0) {
+    const IpRun run = ip_run(gid, x == 0);
+    if (run.head && gid > 0) {
+      const int len = run.len, x1 = x + len - 1, slot = ip_claim(s_gid, gid);
       const long long cnt = len, sx = (long long)len * x + (long long)len * (len - 1) / 2;
-      const int x1 = x + len - 1, slot = gid & (CCL_SLOTS - 1);
-      const int held = atomicCAS(&s_gid[slot], 0, gid);
-      if (held == 0 || held == gid) {
+      if (slot >= 0) {
         atomicMin(&s_mm[slot][0], z), atomicMin(&s_mm[slot][1], y), atomicMin(&s_mm[slot][2], x);
         atomicMax(&s_mm[slot][3], z), atomicMax(&s_mm[slot][4], y), atomicMax(&s_mm[slot][5], x1);
         atomicAdd(&s_sum[slot][0], (unsigned long long)cnt);
@@ -334,7 +323,7 @@ __global__ __launch_bounds__(CCL_NTHR) void ccl_stats_kernel(const uint8_t* __re
     }
   }
   __syncthreads();
-  for (int s = tid; s < CCL_SLOTS; s += CCL_NTHR)
+  for (int s = tid; s < IP_SLOTS; s += IP_NTHR)
     if (s_gid[s] > 0)
       ccl_row_add(table + (long long)(s_gid[s] - 1) * CCL_NCOL, (long long)s_sum[s][0], s_mm[s][0], s_mm[s][1],
                   s_mm[s][2], s_mm[s][3], s_mm[s][4], s_mm[s][5], (long long)s_sum[s][1], (long long)s_sum[s][2],
@@ -406,17 +395,17 @@ extern "C" int fn_ccl_flatten(void* roots, void* flags, int N, int D, int H, int
 // 2^31); T = rank[N*V - 1] rows; table int64 [T][13], fully rewritten; ids int32 [N*V] or null.
 extern "C" int fn_ccl_stats(const void* labels, const void* roots, const void* rank, void* ids, void* table, int N,
                             int D, int H, int W, long long T, hipStream_t st) {
-  if (!ccl_shape_ok(N, D, H, W) || !labels || !roots || !rank) return -2;
+  if (!ip_shape_ok(N, D, H, W) || !labels || !roots || !rank) return -2;
   const long long V = (long long)D * H * W, total = V * N;
-  if (total >= (1LL << 31) || T < 0 || T > total || (T > 0 && !table)) return -2;
+  if (T < 0 || T > total || (T > 0 && !table)) return -2;
   if (T > 0) {
     hipLaunchKernelGGL(ccl_table_init_kernel, dim3((unsigned)((T * CCL_NCOL + CCL_NTHR - 1) / CCL_NTHR)),
                        dim3(CCL_NTHR), 0, st, (long long*)table, T);
     FN_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(ccl_stats_kernel, dim3((unsigned)((total + CCL_CHUNK - 1) / CCL_CHUNK)), dim3(CCL_NTHR), 0, st,
+  hipLaunchKernelGGL(ccl_stats_kernel, dim3((unsigned)((total + IP_CHUNK - 1) / IP_CHUNK)), dim3(IP_NTHR), 0, st,
                      (const uint8_t*)labels, (const int*)roots, (const int*)rank, (int*)ids, (long long*)table,
-                     (int)total, (int)V, H, W, (int)T);
+                     (int)total, (int)V, H, W, (int)T, ip_recip((int)V), ip_recip(H), ip_recip(W));
   FN_CHECK_LAUNCH();
   return 0;
 }

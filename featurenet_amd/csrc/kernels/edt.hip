@@ -12,21 +12,17 @@
 //                        d2 << 32 | (0xFFFFFFFF - index in the sample) over the instance's voxels,
 //                        the voxels with d2 == 1, the voxels (all 0: no voxel carries the row)
 // Integers only; every result is independent of the order of execution.
-#include "common.h"
+#include "instance_pass.h"
 
-constexpr int EDT_NTHR = 256;
+constexpr int EDT_NTHR = 256;                   // the transform kernels
 constexpr int EDT_NWAVE = EDT_NTHR / FN_WAVE;
 constexpr int EDT_MAX_S = 256;                  // longest axis
 constexpr int EDT_PIECES = EDT_MAX_S / FN_WAVE; // 64-wide pieces of a row
 constexpr int EDT_INF = 1 << 30;
 constexpr int EDT_NONE16 = 0xFFFF;              // "no seed in this row" among the uint16 row distances (255^2 < it)
 constexpr int EDT_NCOL = 3;                     // key wall voxels
-constexpr int EDT_SLOTS = 512;                  // LDS instance table, direct-mapped by table row
-constexpr int EDT_CHUNK = 16 * EDT_NTHR;        // voxels per workgroup of the statistics
-static_assert((EDT_SLOTS & (EDT_SLOTS - 1)) == 0 && EDT_NTHR % FN_WAVE == 0 && EDT_MAX_S % FN_WAVE == 0, "shape");
+static_assert(EDT_NTHR % FN_WAVE == 0 && EDT_MAX_S % FN_WAVE == 0, "shape");
 static_assert((EDT_MAX_S - 1) * (EDT_MAX_S - 1) < EDT_NONE16, "a squared row distance fits uint16");
-
-#define EDT_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // ---------------------------------------------------------------------------------------------
 // Transform
@@ -122,76 +118,54 @@ __global__ __launch_bounds__(EDT_NTHR) void edt_init_kernel(unsigned long long* 
   if (i < T * EDT_NCOL) raw[i] = 0;
 }
 
-// g / d for 0 <= g < 2^31 from r = floor(2^32 / d), d >= 2 (as access.hip: the high word of g * r is
-// the quotient or one less, which the remainder tells).
-static unsigned edt_recip(int d) { return d >= 2 ? (unsigned)((1ull << 32) / (unsigned)d) : 0u; }
-__device__ __forceinline__ int edt_div(int g, int d, unsigned r) {
-  const unsigned q = d == 1 ? (unsigned)g : __umulhi((unsigned)g, r);
-  return (int)(q + ((unsigned)g - q * (unsigned)d >= (unsigned)d));
-}
-
-// One lane per voxel, EDT_CHUNK consecutive voxels (of the flat [N*V] range, < 2^31) per workgroup,
-// as access_stats_kernel.  ids int32 [N*V]: per-sample ids from 1, 0 = none; offsets int64 [N+1]; a
-// voxel with id > 0 counts in the 1-based row offsets[n] + id (a row outside [1, T] counts nowhere).
-// A voxel's key d2 << 32 | (0xFFFFFFFF - index in the sample) is positive, and the largest key of an
-// instance names its largest d2 and, among the voxels that attain it, the smallest index, whatever
-// the order of the updates.  A run of one row number within a wave (it breaks at lane 0 and where
-// the row number changes) adds its voxel and wall counts once, by its first lane.  The updates of a
-// workgroup meet in an LDS table of EDT_SLOTS rows first (a slot held by another row sends the
-// update to global memory directly); each occupied slot then goes to raw.
-__global__ __launch_bounds__(EDT_NTHR) void edt_stats_kernel(const int* __restrict__ ids,
-                                                             const long long* __restrict__ offsets,
-                                                             const int* __restrict__ d2, unsigned long long* raw,
-                                                             int total, int V, int T, unsigned rV) {
-  __shared__ int s_gid[EDT_SLOTS];
-  __shared__ unsigned long long s_key[EDT_SLOTS];
-  __shared__ unsigned s_cnt[EDT_SLOTS][2];
-  const int tid = threadIdx.x, lane = tid & 63;
-  for (int s = tid; s < EDT_SLOTS; s += EDT_NTHR) s_gid[s] = 0, s_key[s] = 0, s_cnt[s][0] = 0, s_cnt[s][1] = 0;
+// The instance pass of instance_pass.h.  ids int32 [N*V]: per-sample ids from 1, 0 = none; offsets
+// int64 [N+1]: the rows of each sample (ip_row).  A voxel's key d2 << 32 | (0xFFFFFFFF - index in
+// the sample) is positive, and the largest key of an instance names its largest d2 and, among the
+// voxels that attain it, the smallest index, whatever the order of the updates: EVERY voxel of a
+// row sends its key; the run's first lane adds the voxel and wall counts as well.
+__global__ __launch_bounds__(IP_NTHR) void edt_stats_kernel(const int* __restrict__ ids,
+                                                            const long long* __restrict__ offsets,
+                                                            const int* __restrict__ d2, unsigned long long* raw,
+                                                            int total, int V, int T, unsigned rV) {
+  __shared__ int s_gid[IP_SLOTS];
+  __shared__ unsigned long long s_key[IP_SLOTS];
+  __shared__ unsigned s_cnt[IP_SLOTS][2];
+  const int tid = threadIdx.x;
+  for (int s = tid; s < IP_SLOTS; s += IP_NTHR) s_gid[s] = 0, s_key[s] = 0, s_cnt[s][0] = 0, s_cnt[s][1] = 0;
   __syncthreads();
-  const int g0 = blockIdx.x * EDT_CHUNK;        // (total < 2^31 and the grid covers it: no overflow below)
-  for (int it = 0; it < EDT_CHUNK / EDT_NTHR; ++it) {
-    const unsigned gu = (unsigned)g0 + (unsigned)(it * EDT_NTHR + tid);
-    const bool valid = gu < (unsigned)total;
-    const int g = valid ? (int)gu : total - 1;
-    const int n = edt_div(g, V, rV);
-    const int id = ids[g];
-    const long long row = offsets[n] + id;
-    const bool on = valid && id > 0 && row >= 1 && row <= T;
-    const int gid = on ? (int)row : 0;
+  for (int it = 0; it < IP_CHUNK / IP_NTHR; ++it) {
+    const auto [g, valid] = ip_voxel(it, total);
+    const int n = ip_div(g, V, rV);
+    const int gid = ip_row(offsets, n, ids[g], valid, T);
     const int d = d2[g];
     const unsigned long long key = (unsigned long long)(unsigned)d << 32 | (0xFFFFFFFFu - (unsigned)(g - n * V));
     const unsigned long long b_wall = __ballot(d == 1);
-    const int prev = __shfl_up(gid, 1, 64);
-    const unsigned long long heads = __ballot(lane == 0 || gid != prev);
-    const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
-    const int len = (above ? __builtin_ctzll(above) : 64) - lane;
+    // no break at x == 0: the counts need no coordinate, so a run may go on into the next row of W
+    // (into the next sample it cannot: the row number changes), and x is never computed
+    const auto [head, len, run] = ip_run(gid, false);
     if (gid > 0) {
-      const bool head = (heads >> lane) & 1;
-      const unsigned long long run = (len == 64 ? ~0ull : (1ull << len) - 1) << lane;   // (a head's lanes)
       const unsigned wall = head ? (unsigned)__popcll(b_wall & run) : 0u, vox = head ? (unsigned)len : 0u;
-      const int slot = gid & (EDT_SLOTS - 1);
-      const int held = atomicCAS(&s_gid[slot], 0, gid);
-      if (held == 0 || held == gid) {
+      const int slot = ip_claim(s_gid, gid);
+      if (slot >= 0) {
         atomicMax(&s_key[slot], key);
         if (wall) atomicAdd(&s_cnt[slot][0], wall);
         if (vox) atomicAdd(&s_cnt[slot][1], vox);
       } else {
         unsigned long long* dst = raw + (long long)(gid - 1) * EDT_NCOL;
-        __hip_atomic_fetch_max(&dst[0], key, EDT_RLX_AGENT);
-        if (wall) __hip_atomic_fetch_add(&dst[1], (unsigned long long)wall, EDT_RLX_AGENT);
-        if (vox) __hip_atomic_fetch_add(&dst[2], (unsigned long long)vox, EDT_RLX_AGENT);
+        __hip_atomic_fetch_max(&dst[0], key, IP_RLX_AGENT);
+        if (wall) __hip_atomic_fetch_add(&dst[1], (unsigned long long)wall, IP_RLX_AGENT);
+        if (vox) __hip_atomic_fetch_add(&dst[2], (unsigned long long)vox, IP_RLX_AGENT);
       }
     }
   }
   __syncthreads();
-  for (int s = tid; s < EDT_SLOTS; s += EDT_NTHR) {
+  for (int s = tid; s < IP_SLOTS; s += IP_NTHR) {
     const int gid = s_gid[s];
     if (gid <= 0) continue;
     unsigned long long* dst = raw + (long long)(gid - 1) * EDT_NCOL;
-    __hip_atomic_fetch_max(&dst[0], s_key[s], EDT_RLX_AGENT);
-    if (s_cnt[s][0]) __hip_atomic_fetch_add(&dst[1], (unsigned long long)s_cnt[s][0], EDT_RLX_AGENT);
-    if (s_cnt[s][1]) __hip_atomic_fetch_add(&dst[2], (unsigned long long)s_cnt[s][1], EDT_RLX_AGENT);
+    __hip_atomic_fetch_max(&dst[0], s_key[s], IP_RLX_AGENT);
+    if (s_cnt[s][0]) __hip_atomic_fetch_add(&dst[1], (unsigned long long)s_cnt[s][0], IP_RLX_AGENT);
+    if (s_cnt[s][1]) __hip_atomic_fetch_add(&dst[2], (unsigned long long)s_cnt[s][1], IP_RLX_AGENT);
   }
 }
 
@@ -200,11 +174,10 @@ __global__ __launch_bounds__(EDT_NTHR) void edt_stats_kernel(const int* __restri
 // ---------------------------------------------------------------------------------------------
 
 static bool edt_shape_ok(int N, int D, int H, int W) {
-  if (N < 1 || D < 1 || H < 1 || W < 1 || D > EDT_MAX_S || H > EDT_MAX_S || W > EDT_MAX_S) return false;
-  return (long long)D * H * W * N < (1LL << 31);
+  return ip_shape_ok(N, D, H, W) && D <= EDT_MAX_S && H <= EDT_MAX_S && W <= EDT_MAX_S;
 }
 
-extern "C" void fn_edt_chunk(int* t) { t[0] = EDT_CHUNK, t[1] = EDT_SLOTS; }
+extern "C" void fn_edt_chunk(int* t) { t[0] = IP_CHUNK, t[1] = IP_SLOTS; }
 
 // seeds uint8 [N][D][H][W]; t, d2 int32 [N][D][H][W] (4-byte aligned; they may be one buffer).  passes: bit 0 runs
 // edt_xy_kernel (seeds -> t), bit 1 edt_z_kernel (t -> d2); each writes its output in full.
@@ -239,9 +212,9 @@ extern "C" int fn_edt_stats(const void* ids, const void* offsets, const void* d2
                        st, (unsigned long long*)raw, T);
     FN_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(edt_stats_kernel, dim3((unsigned)((total + EDT_CHUNK - 1) / EDT_CHUNK)), dim3(EDT_NTHR), 0, st,
+  hipLaunchKernelGGL(edt_stats_kernel, dim3((unsigned)((total + IP_CHUNK - 1) / IP_CHUNK)), dim3(IP_NTHR), 0, st,
                      (const int*)ids, (const long long*)offsets, (const int*)d2, (unsigned long long*)raw, (int)total,
-                     (int)V, (int)T, edt_recip((int)V));
+                     (int)V, (int)T, ip_recip((int)V));
   FN_CHECK_LAUNCH();
   return 0;
 }

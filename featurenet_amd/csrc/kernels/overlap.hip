@@ -9,15 +9,9 @@
 // an open-addressing hash table keys uint64 [cap] (0 = empty) / counts int64 [cap], cap a power of
 // two, which the caller has zeroed: the SET of (key, count) pairs in it is exact and does not
 // depend on the order of the atomics; their slots do, so the caller sorts the occupied ones.
-#include "common.h"
+#include "instance_pass.h"
 
-constexpr int OVL_NTHR = 256;
-constexpr int OVL_CHUNK = 16 * OVL_NTHR;        // voxels per workgroup
-constexpr int OVL_SLOTS = 512;                  // LDS (key, count) rows, entered at the key's hash
 constexpr int OVL_LPROBE = 8;                   // LDS slots an update tries before it goes to global memory
-static_assert((OVL_SLOTS & (OVL_SLOTS - 1)) == 0 && OVL_NTHR % FN_WAVE == 0, "table shape");
-
-#define OVL_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // The 64-bit finalizer of MurmurHash3: every output bit depends on every key bit.  The top 9 bits
 // pick the LDS slot, the low bits (cap <= 2^32) the global one.  A single multiplication is not
@@ -46,67 +40,60 @@ __device__ __forceinline__ void ovl_global_add(unsigned long long* keys, long lo
     __hip_atomic_compare_exchange_strong(&keys[h], &held, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
                                          __HIP_MEMORY_SCOPE_AGENT);
     if (held == 0 || held == key) {              // (held keeps 0 when the exchange was made)
-      __hip_atomic_fetch_add(&counts[h], cnt, OVL_RLX_AGENT);
+      __hip_atomic_fetch_add(&counts[h], cnt, IP_RLX_AGENT);
       return;
     }
     h = (h + 1) & mask;
   }
-  __hip_atomic_fetch_add(lost, cnt, OVL_RLX_AGENT);
+  __hip_atomic_fetch_add(lost, cnt, IP_RLX_AGENT);
 }
 
-// One lane per voxel, OVL_CHUNK consecutive voxels (of the flat [N*V] range, < 2^31) per workgroup,
-// as ccl_stats_kernel.  A run of equal keys along a row of W (it breaks at lane 0, at x == 0 and
-// where either id changes) is one update of `len` voxels, made by its first lane; the updates of a
-// workgroup meet in the LDS table first, and each occupied slot makes one global update at the end:
-// two solid volumes make one global update per workgroup, not one per voxel.  An update whose
-// OVL_LPROBE slots from its hash on are all held by other keys goes to the global table directly;
-// that costs the wave a returning global atomic inside the loop, which a strictly direct-mapped
-// table (OVL_LPROBE = 1) pays on most rows already at ~130 keys per chunk (59 against 46 us on
-// the blobs of profiles/feature_match.md).
-__global__ __launch_bounds__(OVL_NTHR) void overlap_pairs_kernel(const int* __restrict__ ids_a,
-                                                                 const int* __restrict__ ids_b,
-                                                                 const long long* __restrict__ off_a,
-                                                                 const long long* __restrict__ off_b,
-                                                                 unsigned long long* keys, long long* counts,
-                                                                 long long* lost, int total, int V, int W,
-                                                                 unsigned long long mask, long long bound) {
-  __shared__ unsigned long long s_key[OVL_SLOTS];
-  __shared__ unsigned long long s_cnt[OVL_SLOTS];
-  const int tid = threadIdx.x, lane = tid & 63;
-  for (int s = tid; s < OVL_SLOTS; s += OVL_NTHR) s_key[s] = 0, s_cnt[s] = 0;
+// The instance pass of instance_pass.h with a 64-bit key for the row number: a run of equal keys
+// along a row of W is one update of `len` voxels, so two solid volumes make one global update per
+// workgroup, not one per voxel.  The LDS table holds (key, count) and is entered at the key's hash,
+// not direct-mapped: an update goes to the global table only when the OVL_LPROBE slots from its
+// hash on are all held by other keys.  That costs the wave a returning global atomic inside the
+// loop, which a strictly direct-mapped table (OVL_LPROBE = 1) pays on most rows already at ~130
+// keys per chunk (59 against 46 us on the blobs of profiles/feature_match.md).
+__global__ __launch_bounds__(IP_NTHR) void overlap_pairs_kernel(const int* __restrict__ ids_a,
+                                                                const int* __restrict__ ids_b,
+                                                                const long long* __restrict__ off_a,
+                                                                const long long* __restrict__ off_b,
+                                                                unsigned long long* keys, long long* counts,
+                                                                long long* lost, int total, int V, int W,
+                                                                unsigned long long mask, long long bound,
+                                                                unsigned rV, unsigned rW) {
+  __shared__ unsigned long long s_key[IP_SLOTS];
+  __shared__ unsigned long long s_cnt[IP_SLOTS];
+  const int tid = threadIdx.x;
+  for (int s = tid; s < IP_SLOTS; s += IP_NTHR) s_key[s] = 0, s_cnt[s] = 0;
   __syncthreads();
-  const int g0 = blockIdx.x * OVL_CHUNK;        // (total < 2^31 and the grid covers it: no overflow below)
-  for (int it = 0; it < OVL_CHUNK / OVL_NTHR; ++it) {
-    const unsigned gu = (unsigned)g0 + (unsigned)(it * OVL_NTHR + tid);
-    const bool valid = gu < (unsigned)total;
-    const int g = valid ? (int)gu : total - 1;
-    const int n = g / V, x = (g - n * V) % W;
+  for (int it = 0; it < IP_CHUNK / IP_NTHR; ++it) {
+    const auto [g, valid] = ip_voxel(it, total);
+    const int n = ip_div(g, V, rV), x = g - ip_div(g, W, rW) * W;           // (V is a multiple of W)
     const int a = ids_a[g], b = ids_b[g];
     const bool on = valid && a > 0 && b > 0;
     const unsigned long long ra = (unsigned long long)(off_a[n] + a), rb = (unsigned long long)(off_b[n] + b);
     const unsigned long long key = on ? (ra << 32) | (rb & 0xffffffffull) : 0ull;
-    const unsigned long long prev = __shfl_up(key, 1, 64);
-    const unsigned long long heads = __ballot(lane == 0 || x == 0 || key != prev);
-    const unsigned long long above = lane == 63 ? 0ull : heads & (~0ull << (lane + 1));
-    const int len = (above ? __builtin_ctzll(above) : 64) - lane;
-    if (((heads >> lane) & 1) && key != 0) {
-      int slot = (int)(ovl_mix(key) >> 55) & (OVL_SLOTS - 1);
+    const IpRun run = ip_run(key, x == 0);
+    if (run.head && key != 0) {
+      int slot = (int)(ovl_mix(key) >> 55) & (IP_SLOTS - 1);
       bool met = false;
       for (int p = 0; p < OVL_LPROBE && !met; ++p) {
         const unsigned long long held = atomicCAS(&s_key[slot], 0ull, key);
         met = held == 0 || held == key;
-        if (met) atomicAdd(&s_cnt[slot], (unsigned long long)len);
-        slot = (slot + 1) & (OVL_SLOTS - 1);
+        if (met) atomicAdd(&s_cnt[slot], (unsigned long long)run.len);
+        slot = (slot + 1) & (IP_SLOTS - 1);
       }
-      if (!met) ovl_global_add(keys, counts, lost, mask, bound, key, len);
+      if (!met) ovl_global_add(keys, counts, lost, mask, bound, key, run.len);
     }
   }
   __syncthreads();
-  for (int s = tid; s < OVL_SLOTS; s += OVL_NTHR)
+  for (int s = tid; s < IP_SLOTS; s += IP_NTHR)
     if (s_key[s] != 0) ovl_global_add(keys, counts, lost, mask, bound, s_key[s], (long long)s_cnt[s]);
 }
 
-extern "C" void fn_overlap_chunk(int* t) { t[0] = OVL_CHUNK, t[1] = OVL_SLOTS; }
+extern "C" void fn_overlap_chunk(int* t) { t[0] = IP_CHUNK, t[1] = IP_SLOTS; }
 
 // keys uint64 [cap], counts int64 [cap] and lost int64 [1] are zero on entry (a key or count left
 // from an earlier call is added to).  cap: a power of two in [2, 2^32]; probe >= 1: an update gives
@@ -119,10 +106,10 @@ extern "C" int fn_overlap_pairs(const void* ids_a, const void* ids_b, const void
   if (cap < 2 || cap > (1LL << 32) || (cap & (cap - 1)) != 0 || probe < 1) return -2;
   if (V >= (1LL << 31) || V * N >= (1LL << 31)) return -2;
   const long long total = V * N;
-  hipLaunchKernelGGL(overlap_pairs_kernel, dim3((unsigned)((total + OVL_CHUNK - 1) / OVL_CHUNK)), dim3(OVL_NTHR), 0,
-                     st, (const int*)ids_a, (const int*)ids_b, (const long long*)off_a, (const long long*)off_b,
+  hipLaunchKernelGGL(overlap_pairs_kernel, dim3((unsigned)((total + IP_CHUNK - 1) / IP_CHUNK)), dim3(IP_NTHR), 0, st,
+                     (const int*)ids_a, (const int*)ids_b, (const long long*)off_a, (const long long*)off_b,
                      (unsigned long long*)keys, (long long*)counts, (long long*)lost, (int)total, (int)V, W,
-                     (unsigned long long)(cap - 1), probe < cap ? probe : cap);
+                     (unsigned long long)(cap - 1), probe < cap ? probe : cap, ip_recip((int)V), ip_recip(W));
   FN_CHECK_LAUNCH();
   return 0;
 }

@@ -29,6 +29,7 @@ import torch
 
 from .. import _native
 from . import reference
+from ._volumes import check_batch, check_volume
 
 NCOL = 13          # sample class voxels root z0 y0 x0 z1 y1 x1 sum_z sum_y sum_x
 
@@ -37,9 +38,7 @@ def _check(labels: torch.Tensor, connectivity: int, what: str) -> None:
     if connectivity not in (6, 26):
         raise ValueError(f"{what}: connectivity must be 6 (faces) or 26 (faces, edges and corners), "
                          f"not {connectivity!r}")
-    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.uint8 or labels.dim() != 4:
-        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, torch.Tensor) else type(labels).__name__
-        raise ValueError(f"{what}: labels must be a uint8 [N, D, H, W] tensor, not {got}")
+    check_volume(labels, what, "labels")
     if labels.shape[1] * labels.shape[2] * labels.shape[3] >= 1 << 31:
         raise ValueError(f"{what}: a sample must have fewer than 2^31 voxels")
 
@@ -91,8 +90,7 @@ def instance_table(labels: torch.Tensor, roots: torch.Tensor, want_ids: bool = T
     if labels.numel() == 0:
         return (torch.zeros(labels.shape, dtype=torch.int32, device=dev) if want_ids else None,
                 torch.zeros(0, NCOL, dtype=torch.int64, device=dev), torch.zeros(N + 1, dtype=torch.int64, device=dev))
-    if labels.numel() >= 1 << 31:                # (the kernel ranks the batch's roots in int32)
-        raise ValueError("instance_table: a batch must have fewer than 2^31 voxels; split it by samples")
+    check_batch(labels, "instance_table")        # (the kernel ranks the batch's roots in int32)
     labels = labels.contiguous()
     K_, st = _native.kernels(), _native.stream(labels)
     roots = roots.contiguous()

@@ -17,15 +17,14 @@ import torch
 
 from .. import _native
 from . import reference
+from ._volumes import check_batch, check_ids_offsets, check_volume
 from .reference import EDT_INF, EDT_MAX_S  # noqa: F401
 
 NCOL = 4           # r2 at wall voxels
 
 
 def _check_seeds(seeds, what: str, name: str = "seeds") -> None:
-    if not isinstance(seeds, torch.Tensor) or seeds.dtype != torch.uint8 or seeds.dim() != 4:
-        got = f"{seeds.dtype} {tuple(seeds.shape)}" if isinstance(seeds, torch.Tensor) else type(seeds).__name__
-        raise ValueError(f"{what}: {name} must be a uint8 [N, D, H, W] tensor, not {got}")
+    check_volume(seeds, what, name)
     if max(seeds.shape[1:]) > EDT_MAX_S:
         raise ValueError(f"{what}: each of D, H, W is at most {EDT_MAX_S}, not {tuple(seeds.shape[1:])}")
 
@@ -36,8 +35,7 @@ def distance_sq(seeds: torch.Tensor, border: bool = False) -> torch.Tensor:
     _check_seeds(seeds, "distance_sq")
     if not _native.use_native(seeds) or seeds.numel() == 0:
         return reference.distance_sq(seeds, border)
-    if seeds.numel() >= 1 << 31:
-        raise ValueError("distance_sq: a batch must have fewer than 2^31 voxels; split it by samples")
+    check_batch(seeds, "distance_sq")
     seeds = seeds.contiguous()
     N, D, H, W = seeds.shape
     d2 = torch.empty(seeds.shape, dtype=torch.int32, device=seeds.device)
@@ -55,23 +53,13 @@ def dimension_table(ids: torch.Tensor, offsets: torch.Tensor, occ: torch.Tensor,
     W]``, on the ids' device.  ``rows``: the table's row count ``T = offsets[-1]`` when the caller
     knows it (it saves the device-to-host read that sizes the table)."""
     _check_seeds(occ, "dimension_table", "occ")
-    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.shape != occ.shape:
-        got = f"{ids.dtype} {tuple(ids.shape)}" if isinstance(ids, torch.Tensor) else type(ids).__name__
-        raise ValueError(f"dimension_table: ids must be int32 {tuple(occ.shape)}, not {got}")
-    N = occ.shape[0]
-    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or tuple(offsets.shape) != (N + 1,):
-        got = f"{offsets.dtype} {tuple(offsets.shape)}" if isinstance(offsets, torch.Tensor) else type(offsets).__name__
-        raise ValueError(f"dimension_table: offsets must be int64 [{N + 1}], not {got}")
-    if ids.device != occ.device or offsets.device != occ.device:
-        raise ValueError(f"dimension_table: ids ({ids.device}), offsets ({offsets.device}) and occ ({occ.device}) "
-                         "must be on one device")
+    check_ids_offsets(ids, offsets, occ, "dimension_table")
     if not _native.use_native(ids) or ids.numel() == 0:
         d2 = reference.distance_sq(occ)
         return reference.dimension_table(ids, offsets, d2), (d2 if want_d2 else None)
-    if ids.numel() >= 1 << 31:
-        raise ValueError("dimension_table: a batch must have fewer than 2^31 voxels; split it by samples")
+    check_batch(ids, "dimension_table")
     ids, offsets = ids.contiguous(), offsets.contiguous()
-    _, D, H, W = ids.shape
+    N, D, H, W = ids.shape
     d2 = distance_sq(occ)
     T = int(offsets[-1]) if rows is None else int(rows)
     raw = torch.empty(T, 3, dtype=torch.int64, device=ids.device)

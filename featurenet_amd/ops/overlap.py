@@ -20,16 +20,15 @@ import torch
 
 from .. import _native
 from . import ccl, reference
+from ._volumes import check_batch, check_volume
 
 MIN_CAP = 1024
 PROBE = 256        # slots an update tries before it counts as lost (the last, full-size table: all)
 
 
 def _check(ids_a, off_a, ids_b, off_b) -> None:
-    for name, t in (("ids_a", ids_a), ("ids_b", ids_b)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 4:
-            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
-            raise ValueError(f"overlap_table: {name} must be an int32 [N, D, H, W] tensor, not {got}")
+    check_volume(ids_a, "overlap_table", "ids_a", torch.int32)
+    check_volume(ids_b, "overlap_table", "ids_b", torch.int32)
     if ids_b.shape != ids_a.shape or ids_b.device != ids_a.device:
         raise ValueError(f"overlap_table: ids_b must be int32 {tuple(ids_a.shape)} on {ids_a.device}, not "
                          f"{ids_b.dtype} {tuple(ids_b.shape)} on {ids_b.device}")
@@ -40,8 +39,7 @@ def _check(ids_a, off_a, ids_b, off_b) -> None:
             got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
             raise ValueError(f"overlap_table: {name} must be int64 [{N + 1}] (N + 1 offsets) on {ids_a.device}, "
                              f"not {got}")
-    if ids_a.numel() >= 1 << 31:
-        raise ValueError("overlap_table: a batch must have fewer than 2^31 voxels; split it by samples")
+    check_batch(ids_a, "overlap_table")
 
 
 def instance_overlap(labels_a: torch.Tensor, labels_b: torch.Tensor, background: int | None = 0,
