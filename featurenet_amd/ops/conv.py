@@ -425,6 +425,8 @@ def _halo_call(src5, wmat, bias, out, stats, geom, ncol, act):
 
 
 def halo_conv_fwd(x5, w, bias, spec: ConvSpec, act: int, want_stats: bool, plan):
+    if want_stats and bias is not None:
+        raise ValueError("conv_halo takes BN statistics without a bias (its statistics instance has no bias operand)")
     TD, TH, TW = plan
     geom = [spec.N, spec.D, spec.H, spec.W, spec.C, spec.OD, spec.OH, spec.OW, spec.KD, spec.KH, spec.KW,
             spec.pd, spec.ph, spec.pw, TD, TH, TW]
