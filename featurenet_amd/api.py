@@ -281,7 +281,7 @@ def evaluate_segmentation(model, x, y, batch_size: int = 32, device=None, packed
 @torch.no_grad()
 def extract_features(model, x, batch_size: int = 32, device=None, packed_size: int | None = None,
                      background: int | None = 0, connectivity: int = 6, min_voxels: int = 1,
-                     return_ids: bool = False, access: bool = False, dimensions: bool = False):
+                     return_ids: bool = False, access: bool = False, dimensions: bool = False, tool=None):
     """The machining features of each part -> (one list of :class:`FeatureInstance` per sample,
     ids int32 [N, S, S, S] or None).
 
@@ -305,9 +305,19 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
     ``clearance_at`` the first voxel that attains it, ``wall_voxels`` the voxels with a material
     face neighbour; ``clearance`` and ``tool_diameter`` follow from these.  The distance transform
     runs on the model's device (``ops.edt``); 4 more integers per component cross to the host.
-    """
-    from .utils.seginstances import FeatureInstance
 
+    With ``tool``, the diameter in voxels of a ball-shaped tool (the convention of
+    ``tool_diameter``), every record also says what that tool does to the feature: ``entry2`` is,
+    per face, the largest squared clearance of a straight path from outside that face to one of
+    its voxels (``entry_diameter(face)``), ``reachable`` the voxels the tool's centre reaches
+    from each face, ``unreachable`` those it reaches from none, ``machinable`` the voxels it removes
+    from the centres it reaches (``residual``: the rest); ``tool_faces()`` names the faces it can
+    come from.  Runs on the model's device (``ops.reach``); 15 more integers per component cross
+    to the host.
+    """
+    from .utils.seginstances import FeatureInstance, tool_thresholds
+
+    thresholds = None if tool is None else tool_thresholds(tool)
     if isinstance(model, (str, Path)):
         model, _ = load(model, device)
     if not isinstance(model, FeatureNet3DSeg):
@@ -327,9 +337,12 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
             xb = unpack_voxels(xb, packed_size)
         xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
         table, offsets, idb, *more = model.instances(xb, background=background, connectivity=connectivity,
-                                                     want_ids=return_ids, want_access=access, want_dims=dimensions)
+                                                     want_ids=return_ids, want_access=access, want_dims=dimensions,
+                                                     want_reach=thresholds)
         feats += FeatureInstance.from_table(table, offsets, min_voxels, access=more[0] if access else None,
-                                            dims=more[-1] if dimensions else None, shape=tuple(xb.shape[1:4]))
+                                            dims=more[1 if access else 0] if dimensions else None,
+                                            shape=tuple(xb.shape[1:4]),
+                                            reach=more[-1] if thresholds is not None else None, tool=thresholds)
         if return_ids:
             ids.append(idb.cpu())
     if not return_ids:
@@ -340,7 +353,7 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
 
 @torch.no_grad()
 def label_components(labels, background: int | None = 0, connectivity: int = 6, device=None, occupancy=None,
-                     dimensions: bool = False):
+                     dimensions: bool = False, tool=None):
     """Connected components of label volumes the caller already has (ground truth, say) ->
     (ids int32 [N, D, H, W], one list of :class:`FeatureInstance` per sample).
 
@@ -349,14 +362,18 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     defaults to the GPU when there is one (the ``ccl`` kernels), else the CPU reference path.
     ``occupancy``, an integer or bool array of the labels' shape (material: non-zero), adds the
     access counts to the records as :func:`extract_features` does with ``access``; ``dimensions``
-    (which needs ``occupancy``) adds the clear widths as its ``dimensions`` does.
+    (which needs ``occupancy``) adds the clear widths as its ``dimensions`` does, ``tool`` (a
+    diameter in voxels, which needs ``occupancy`` too) the reach of that tool as its ``tool`` does.
     """
-    from .ops import access, ccl, edt
-    from .utils.seginstances import FeatureInstance
+    from .ops import access, ccl, edt, reach
+    from .utils.seginstances import FeatureInstance, tool_thresholds
 
     if dimensions and occupancy is None:
         raise ValueError("label_components(): dimensions=True needs occupancy (the material the widths are "
                          "measured against)")
+    if tool is not None and occupancy is None:
+        raise ValueError("label_components(): tool needs occupancy (the material the tool must clear)")
+    thresholds = None if tool is None else tool_thresholds(tool)
 
     lt = torch.as_tensor(np.asarray(labels)) if not isinstance(labels, torch.Tensor) else labels
     if lt.is_floating_point() or lt.dtype == torch.bool:
@@ -379,14 +396,40 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     lt = lt.to(device).to(torch.uint8).contiguous()
     roots, flags = ccl.connected_components(lt, background, connectivity, return_flags=True)
     ids, table, offsets = ccl.instance_table(lt, roots, want_ids=True, flags=flags)
-    acc = dim = None
+    acc = dim = rch = d2 = None
     if ot is not None:
         occ = (ot.to(device) != 0).to(torch.uint8)
         acc, _ = access.access_table(ids, offsets, occ, rows=table.shape[0])
         if dimensions:
-            dim, _ = edt.dimension_table(ids, offsets, occ, rows=table.shape[0])
+            dim, d2 = edt.dimension_table(ids, offsets, occ, rows=table.shape[0], want_d2=thresholds is not None)
+        if thresholds is not None:
+            rch, _ = reach.reach_table(ids, offsets, occ, *thresholds, rows=table.shape[0], d2=d2)
     return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets, access=acc, dims=dim,
-                                                         shape=tuple(lt.shape[1:]))
+                                                         shape=tuple(lt.shape[1:]), reach=rch, tool=thresholds)
+
+
+@torch.no_grad()
+def tool_reach(voxels, device=None):
+    """Directional clearance -> int32 ``[N, 6, D, H, W]`` (or ``[6, D, H, W]`` for one ``[D, H, W]``
+    volume): for each face ``+z, -z, +x, -x, +y, -y`` of the grid (``+z`` the high-index end) the
+    squared clearance of the largest ball whose centre can travel in a straight line from outside
+    that face to the voxel -- the smallest :func:`distance_transform` value (``border=False``) on
+    the way, the voxel included.  0 on material (non-zero ``voxels``), :data:`EDT_INF` in a sample
+    without any.  Each axis is at most 256 long.  ``device`` defaults to the GPU when there is one
+    (the ``edt`` and ``reach`` kernels), else the CPU reference path; the result is the same.
+    """
+    from .ops import edt, reach
+
+    vt = torch.as_tensor(np.asarray(voxels)) if not isinstance(voxels, torch.Tensor) else voxels
+    if vt.is_floating_point() or vt.is_complex():
+        raise ValueError(f"tool_reach(): voxels must be integers or bools, not {vt.dtype}")
+    if vt.dim() not in (3, 4):
+        raise ValueError(f"tool_reach(): voxels must be [D, H, W] or [N, D, H, W], not {tuple(vt.shape)}")
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    occ = (vt.to(device) != 0).to(torch.uint8)
+    r6 = reach.reach_scan(edt.distance_sq(occ if vt.dim() == 4 else occ[None]))
+    return (r6 if vt.dim() == 4 else r6[0]).cpu().numpy()
 
 
 @torch.no_grad()

@@ -246,7 +246,7 @@ def cmd_features(a) -> int:
     feats, ids = api.extract_features(a.model, x, packed_size=a.packed_size,
                                       background=None if a.background < 0 else a.background,
                                       connectivity=a.connectivity, min_voxels=a.min_voxels, return_ids=bool(a.ids),
-                                      access=a.access, dimensions=a.dimensions)
+                                      access=a.access, dimensions=a.dimensions, tool=a.tool)
     if a.ids:
         np.save(a.ids, ids)
     summary = json.dumps({"samples": [[f.to_dict(a.access_fraction) for f in fs] for fs in feats]})
@@ -269,6 +269,27 @@ def cmd_distance(a) -> int:
     summary = json.dumps({"shape": list(d2.shape), "seeds": int((d2 == 0).sum()),
                           "max_distance_sq": int(finite.max()) if finite.size else None,
                           "unreached_voxels": int((d2 >= api.EDT_INF).sum())})
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(summary + "\n")
+    print(summary)
+    return 0
+
+
+def cmd_reach(a) -> int:
+    import numpy as np
+
+    from . import api
+    from .utils.partfeatures import FACES
+
+    vol = np.load(a.input, allow_pickle=False)
+    r6 = api.tool_reach(vol, device=a.device or None)
+    np.save(a.output, r6)
+    faces = np.moveaxis(r6, -4, 0).reshape(6, -1)
+    summary = json.dumps({"shape": list(r6.shape), "material": int(np.count_nonzero(vol)),
+                          "open_voxels": {f: int((faces[k] >= 1).sum()) for k, f in enumerate(FACES)},
+                          "max_entry_sq": {f: (int(faces[k].max()) if faces[k].size and faces[k].max() < api.EDT_INF
+                                               else None) for k, f in enumerate(FACES)}})
     if a.json:
         with open(a.json, "w") as f:
             f.write(summary + "\n")
@@ -529,7 +550,20 @@ def build_parser() -> argparse.ArgumentParser:
     ft.add_argument("--dimensions", action="store_true",
                     help="add the clear widths: clearance2 (largest squared distance to the material), clearance_at, "
                          "tool_diameter, wall_voxels")
+    ft.add_argument("--tool", type=float, default=None, metavar="T",
+                    help="add the reach of a ball-shaped tool of diameter T voxels: entry2 and reachable per face, "
+                         "tool_faces (at --access-fraction), unreachable, machinable, residual")
     ft.set_defaults(fn=cmd_features)
+
+    rc = sub.add_parser("reach", help="directional clearance: the squared clearance of the largest ball that reaches "
+                                      "each voxel in a straight line from each face -> int32 .npy")
+    rc.add_argument("input", help="[D, H, W] or [N, D, H, W] integer or bool array (.npy), non-zero = material, each "
+                                  "axis at most 256")
+    rc.add_argument("-o", "--output", required=True,
+                    help="r6, int32 [6, D, H, W] or [N, 6, D, H, W], faces +z -z +x -x +y -y (.npy)")
+    rc.add_argument("--device", default="", help="cuda / cpu (default: the GPU when there is one)")
+    rc.add_argument("--json", default="", metavar="OUT", help="also write the summary to this file")
+    rc.set_defaults(fn=cmd_reach)
 
     dt = sub.add_parser("distance", help="exact squared Euclidean distance to the nearest non-zero voxel -> int32 .npy")
     dt.add_argument("input", help="[D, H, W] or [N, D, H, W] integer or bool array (.npy), each axis at most 256")

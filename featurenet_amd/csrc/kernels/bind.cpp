@@ -59,6 +59,10 @@ int fn_access_stats(const void*, const void*, const void*, const void*, const vo
 void fn_edt_chunk(int*);
 int fn_edt_transform(const void*, void*, void*, int, int, int, int, int, int, hipStream_t);
 int fn_edt_stats(const void*, const void*, const void*, void*, int, int, int, int, long long, hipStream_t);
+void fn_reach_chunk(int*);
+int fn_reach_scan(const void*, void*, int, int, int, int, hipStream_t);
+int fn_reach_stats(const void*, const void*, const void*, const void*, void*, int, int, int, int, long long, int, int,
+                   hipStream_t);
 int fn_pw_wgrad(const void*, const void*, float*, long long, int, int, hipStream_t, const float*, const float*, int,
                 float*);
 int fn_pw_wgrad_blocks(long long, int, int);
@@ -817,6 +821,37 @@ PYBIND11_MODULE(_C, m) {
         "edt_stats");
   }, py::arg("ids"), py::arg("offsets"), py::arg("d2"), py::arg("raw"), py::arg("N"), py::arg("D"), py::arg("H"),
      py::arg("W"), py::arg("T"), py::arg("st"), py::arg("ext"));
+  // tool reach of feature instances (reach.hip): vol int32 [N][D][H][W], D, H, W <= 256; r6 int32 [N][6][D][H][W]
+  // (written in full): the minimum of vol from each voxel to face k (+z -z +x -x +y -y) of the grid along that face's
+  // axis, the voxel included; ext = {numel(vol), numel(r6)}
+  m.def("reach_chunk", []() {
+    int t[2];
+    fn_reach_chunk(t);
+    return py::make_tuple(t[0], t[1]);
+  });
+  m.def("reach_scan", [](uintptr_t vol, uintptr_t r6, int N, int D, int H, int W, uintptr_t st,
+                         std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "reach_scan", "vol");
+    fits(ext, 1, prod({N, 6, D, H, W}), "reach_scan", "r6");
+    chk(fn_reach_scan(P<const void*>(vol), P<void*>(r6), N, D, H, W, S(st)), "reach_scan");
+  }, py::arg("vol"), py::arg("r6"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("st"),
+     py::arg("ext"));
+  // ids int32 [N*V] and offsets int64 [N+1] as for access_stats, r6 int32 [N][6][V] (>= 0) as reach_scan writes it,
+  // dc2 int32 [N*V]; raw int64 [T][15] (fully rewritten): the largest r6[k] over the row's voxels (0..5; -1: no voxel
+  // carries the row), its voxels with r6[k] >= need2 (6..11), with no such k (12), with dc2 <= cut2 (13), its voxels
+  // (14); need2 >= 1, cut2 >= 0; ext = {numel(ids), numel(offsets), numel(r6), numel(dc2), numel(raw)}
+  m.def("reach_stats", [](uintptr_t ids, uintptr_t offsets, uintptr_t r6, uintptr_t dc2, uintptr_t raw, int N, int D,
+                          int H, int W, long long T, int need2, int cut2, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "reach_stats", "ids");
+    fits(ext, 1, N < 0 ? -1 : N + 1LL, "reach_stats", "offsets");
+    fits(ext, 2, prod({N, 6, D, H, W}), "reach_stats", "r6");
+    fits(ext, 3, prod({N, D, H, W}), "reach_stats", "dc2");
+    fits(ext, 4, prod({T, 15}), "reach_stats", "raw");
+    chk(fn_reach_stats(P<const void*>(ids), P<const void*>(offsets), P<const void*>(r6), P<const void*>(dc2),
+                       P<void*>(raw), N, D, H, W, T, need2, cut2, S(st)),
+        "reach_stats");
+  }, py::arg("ids"), py::arg("offsets"), py::arg("r6"), py::arg("dc2"), py::arg("raw"), py::arg("N"), py::arg("D"),
+     py::arg("H"), py::arg("W"), py::arg("T"), py::arg("need2"), py::arg("cut2"), py::arg("st"), py::arg("ext"));
   // multi-feature parts from their parameter tables (partgen.hip): params int32 [N][K][16]; occ / labels / slots
   // uint8 [N][S][S][S] (8-byte aligned) and packed uint8 [N][S^3/8], each 0 = not wanted; S % 8 == 0, 8 <= S <=
   // 256, K <= 32; ext = {numel(params), numel(occ), numel(packed), numel(labels), numel(slots)}

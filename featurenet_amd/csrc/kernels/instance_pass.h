@@ -1,6 +1,6 @@
-// The per-voxel pass under the four instance-table kernels: ccl_stats_kernel (ccl.hip),
-// overlap_pairs_kernel (overlap.hip), access_stats_kernel (access.hip), edt_stats_kernel (edt.hip).
-// What they share, and what a fifth must keep:
+// The per-voxel pass under the five instance-table kernels: ccl_stats_kernel (ccl.hip),
+// overlap_pairs_kernel (overlap.hip), access_stats_kernel (access.hip), edt_stats_kernel (edt.hip),
+// reach_stats_kernel (reach.hip).  What they share, and what a sixth must keep:
 //   * one lane per voxel; a workgroup takes IP_CHUNK consecutive voxels of the flat [N*V] range
 //     (N*V < 2^31: ip_shape_ok), IP_NTHR at a time;
 //   * the spare lanes of the last workgroup are clamped onto the last voxel: they read it, take part

@@ -260,7 +260,8 @@ class FeatureNet3DSeg(nn.Module):
 
     @torch.no_grad()
     def instances(self, x: torch.Tensor, background: int | None = 0, connectivity: int = 6,
-                  want_ids: bool = False, want_access: bool = False, want_dims: bool = False):
+                  want_ids: bool = False, want_access: bool = False, want_dims: bool = False,
+                  want_reach: tuple | None = None):
         """The features in each sample: :meth:`predict`'s labels split into connected components
         -> ``(table, offsets, ids or None)`` on the model's device.  ``table`` int64 ``[T, 13]``
         has one row per component (``sample, class, voxels, root, z0, y0, x0, z1, y1, x1, sum_z,
@@ -277,16 +278,23 @@ class FeatureNet3DSeg(nn.Module):
         With ``want_dims`` ``dim`` int64 ``[T, 4]`` is appended (after ``acc`` when that is there):
         row by row of ``table`` the largest squared distance from one of the component's voxels
         to the material, the smallest index ``(z * S + y) * S + x`` of a voxel that attains it,
-        the component's voxels with a material face neighbour, and all of them (``ops.edt``)."""
-        from ..ops import access, ccl, edt
+        the component's voxels with a material face neighbour, and all of them (``ops.edt``).
+
+        With ``want_reach = (need2, cut2)``, a tool (``utils.seginstances.tool_thresholds``),
+        ``reach`` int64 ``[T, 15]`` is appended (after ``acc`` and ``dim``): row by row of ``table``
+        the largest squared clearance of a straight path from each face to one of the component's
+        voxels, the voxels the tool's centre reaches from each face and from none, the voxels the
+        tool clears, and all of them (``ops.reach``).  It shares the distance transform of
+        ``want_dims``."""
+        from ..ops import access, ccl, edt, reach
 
         if connectivity not in (6, 26):
             raise ValueError(f"instances: connectivity must be 6 or 26, not {connectivity!r}")
         labels = self.predict(x)
         roots, flags = ccl.connected_components(labels, background, connectivity, return_flags=True)
-        ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids or want_access or want_dims,
-                                                 flags=flags)
-        if not (want_access or want_dims):
+        more = want_access or want_dims or want_reach is not None
+        ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids or more, flags=flags)
+        if not more:
             return table, offsets, ids
         occ = (x != 0).to(device=labels.device, dtype=torch.uint8)
         if occ.dim() == 5:                       # [N, S, S, S, C]: material in any channel
@@ -295,8 +303,13 @@ class FeatureNet3DSeg(nn.Module):
         out = [table, offsets, ids if want_ids else None]
         if want_access:
             out.append(access.access_table(ids, offsets, occ, rows=table.shape[0])[0])
+        d2 = None
         if want_dims:
-            out.append(edt.dimension_table(ids, offsets, occ, rows=table.shape[0])[0])
+            dim, d2 = edt.dimension_table(ids, offsets, occ, rows=table.shape[0], want_d2=want_reach is not None)
+            out.append(dim)
+        if want_reach is not None:
+            need2, cut2 = want_reach
+            out.append(reach.reach_table(ids, offsets, occ, need2, cut2, rows=table.shape[0], d2=d2)[0])
         return tuple(out)
 
     def match(self, x: torch.Tensor, y: torch.Tensor, background: int | None = 0, connectivity: int = 6):

@@ -1,4 +1,4 @@
-"""Argument checks shared by the volume ops (``ccl``, ``overlap``, ``access``, ``edt``).  ``what`` is the
+"""Argument checks shared by the volume ops (``ccl``, ``overlap``, ``access``, ``edt``, ``reach``).  ``what`` is the
 public function's name: every message starts with it."""
 import torch
 

@@ -374,6 +374,73 @@ def dimension_table(ids: torch.Tensor, offsets: torch.Tensor, d2: torch.Tensor) 
     return dim
 
 
+REACH_NCOL = 15            # entry2 of the six faces, reached from each, from none, machinable, voxels
+
+
+def reach_scan(vol: torch.Tensor) -> torch.Tensor:
+    """Directional minima of ``vol`` int32 ``[N, D, H, W]`` -> ``r6`` int32 ``[N, 6, D, H, W]``:
+    ``r6[n, k, v]`` is the smallest ``vol[n]`` over the voxels from ``v`` to face ``k`` of the grid
+    (``+z, -z, +x, -x, +y, -y``; ``+z`` the high-index end) along that face's axis, ``v`` included.
+    Over ``vol = distance_sq(occ)`` it is the squared clearance of the largest ball whose centre
+    travels in a straight line from outside face ``k`` to ``v``.  Each axis is at most
+    ``EDT_MAX_S``.  ``torch.cummin`` along the axis, on a flipped view for the ``+`` faces: the
+    oracle of ``reach_scan`` (kernel) and the CPU path of ``ops.reach.reach_scan``."""
+    if vol.dim() != 4 or vol.dtype != torch.int32:
+        raise ValueError(f"reach_scan: vol must be int32 [N, D, H, W], not {vol.dtype} {tuple(vol.shape)}")
+    if max(vol.shape[1:]) > EDT_MAX_S:
+        raise ValueError(f"reach_scan: each of D, H, W is at most {EDT_MAX_S}, not {tuple(vol.shape[1:])}")
+    if vol.numel() == 0:
+        return vol.new_zeros((vol.shape[0], 6) + tuple(vol.shape[1:]))
+    out = []
+    for axis in (1, 3, 2):
+        out.append(vol.flip(axis).cummin(axis).values.flip(axis))
+        out.append(vol.cummin(axis).values)
+    return torch.stack(out, 1)
+
+
+def reach_seeds(r6: torch.Tensor, need2: int) -> torch.Tensor:
+    """uint8 ``[N, D, H, W]``: 1 where a tool that needs the squared clearance ``need2`` reaches the
+    voxel with its centre from at least one face (``r6[:, k] >= need2`` for some ``k``)."""
+    return (r6 >= need2).any(1).to(torch.uint8)
+
+
+def reach_table(ids: torch.Tensor, offsets: torch.Tensor, r6: torch.Tensor, dc2: torch.Tensor, need2: int,
+                cut2: int) -> torch.Tensor:
+    """Reach table of an instance-id volume for one tool -> int64 ``[T, 15]``.
+
+    ``ids`` int32 ``[N, D, H, W]`` and ``offsets`` int64 ``[N + 1]`` as :func:`instance_table` gives
+    them (``T = offsets[-1]``); ``r6`` = :func:`reach_scan` of ``distance_sq(occ)``; ``dc2`` =
+    ``distance_sq(reach_seeds(r6, need2))``, the squared distance to the nearest centre the tool
+    reaches.  The tool, a ball of diameter ``t``, enters as ``need2 = ceil(((t + 1) / 2)^2) >= 1``
+    (a centre is admissible from face ``k`` iff ``r6[k] >= need2``) and ``cut2 = floor((t / 2)^2)
+    >= 0`` (at a centre it removes the voxels within squared distance ``cut2``).  Row ``offsets[n]
+    + id - 1`` holds, of id ``id`` of sample ``n``: the largest ``r6[k]`` over its voxels (columns
+    0..5), its voxels with ``r6[k] >= need2`` (6..11), with no such ``k`` (12), with ``dc2 <=
+    cut2`` (13: machinable) and all of them (14).  A row that no voxel carries holds -1 in columns
+    0..5 and 0 elsewhere; a voxel with id 0 or whose row lies outside the table counts nowhere.
+    Exact integers: the oracle of ``reach_stats`` and the CPU path of ``ops.reach.reach_table``."""
+    if need2 < 1 or cut2 < 0:
+        raise ValueError(f"reach_table: need2 >= 1 and cut2 >= 0, not {need2}, {cut2}")
+    N = ids.shape[0]
+    dev = ids.device
+    T = int(offsets[-1])
+    row = ids.to(torch.int64) + offsets.to(torch.int64)[:-1].view(N, 1, 1, 1) - 1
+    fg = (ids > 0) & (row >= 0) & (row < T)
+    out = torch.zeros(T, REACH_NCOL, dtype=torch.int64, device=dev)
+    if T:
+        rows = row[fg]
+        none = torch.ones_like(rows, dtype=torch.bool)
+        for k in range(6):
+            e = r6[:, k].to(torch.int64)[fg]
+            out[:, k] = torch.full((T,), -1, dtype=torch.int64, device=dev).scatter_reduce(0, rows, e, "amax")
+            out[:, 6 + k] = torch.bincount(rows[e >= need2], minlength=T)
+            none &= e < need2
+        out[:, 12] = torch.bincount(rows[none], minlength=T)
+        out[:, 13] = torch.bincount(rows[dc2[fg] <= cut2], minlength=T)
+        out[:, 14] = torch.bincount(rows, minlength=T)
+    return out
+
+
 def _part_volume(cls: int, f: dict, X, Y, Z, top: int):
     """The volume of one feature class over canonical quarter-voxel coordinates ``X, Y, Z``
     (int64 ``[n, S, S, S]``); ``f`` maps the field names of a table row to ``[n, 1, 1, 1]``."""

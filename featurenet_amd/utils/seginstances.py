@@ -3,12 +3,14 @@
 One :class:`FeatureInstance` per row of the instance table (``ops.ccl.instance_table``): exact
 integer counts and bounds, the centroid as ``sum / voxels`` in float64 on the host; with an access
 table (``ops.access.access_table``) also the voxels open toward each face of the grid; with a dimension table (``ops.edt.dimension_table``) also its clear width: the
-largest squared distance from one of its voxels to the material, and where that voxel lies.
+largest squared distance from one of its voxels to the material, and where that voxel lies; with a
+reach table (``ops.reach.reach_table``) also what a given tool reaches from each face and clears.
 """
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass
+from fractions import Fraction
 
 import numpy as np
 
@@ -17,6 +19,26 @@ from ..ops.reference import EDT_INF
 from .partfeatures import FACES
 
 _AXIS = {"z": 0, "y": 1, "x": 2}
+
+
+def tool_thresholds(t) -> tuple:
+    """``(need2, cut2)`` of a ball-shaped tool of diameter ``t`` voxels (the convention of
+    ``FeatureInstance.tool_diameter``), in exact arithmetic: the tool's centre may stand on a voxel
+    whose squared distance to the material is at least ``need2 = ceil(((t + 1) / 2)^2)``, and from
+    there it removes the voxels within squared distance ``cut2 = floor((t / 2)^2)``.  ``t`` is an
+    int, a float (taken at its exact binary value), a ``Fraction`` or a decimal string, ``>= 0``."""
+    if isinstance(t, bool):
+        raise ValueError(f"tool_thresholds: the tool diameter must be a number, not {t!r}")
+    try:
+        d = Fraction(t)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"tool_thresholds: the tool diameter must be a finite number, not {t!r}") from None
+    if d < 0:
+        raise ValueError(f"tool_thresholds: the tool diameter must be >= 0, not {t!r}")
+    need2, cut2 = math.ceil(((d + 1) / 2) ** 2), math.floor((d / 2) ** 2)
+    if need2 >= EDT_INF:
+        raise ValueError(f"tool_thresholds: a tool of diameter {t!r} is wider than any grid")
+    return need2, cut2
 
 
 @dataclass
@@ -32,6 +54,11 @@ class FeatureInstance:
     clearance2: int | None = None  # the largest squared distance from a voxel's centre to a material voxel's
     clearance_at: tuple | None = None   # (z, y, x) of the first voxel, in raster order, that attains it
     wall_voxels: int | None = None      # its voxels with a material face neighbour
+    entry2: tuple | None = None    # per face, the largest squared clearance of a straight path from that face to a voxel
+    reachable: tuple | None = None      # per face, its voxels the tool's centre reaches from that face
+    unreachable: int | None = None      # its voxels the tool's centre reaches from no face
+    machinable: int | None = None       # its voxels the tool removes from the centres it reaches
+    tool: tuple | None = None      # (need2, cut2) of the tool these counts were made for
 
     @property
     def clearance(self) -> float | None:
@@ -47,6 +74,29 @@ class FeatureInstance:
         material voxel: ``max(0, 2 * clearance - 1)``; None without dimensions."""
         c = self.clearance
         return None if c is None else max(0.0, 2.0 * c - 1.0)
+
+    def entry_diameter(self, face: str) -> float | None:
+        """The diameter in voxels of the largest ball that reaches at least one voxel of the feature
+        in a straight line from ``face``: ``max(0, 2 * sqrt(entry2) - 1)`` (``inf`` in a part without
+        material); None without reach."""
+        if face not in FACES:
+            raise ValueError(f"entry_diameter: face must be one of {FACES}, not {face!r}")
+        if self.entry2 is None:
+            return None
+        e = self.entry2[FACES.index(face)]
+        return math.inf if e >= EDT_INF else max(0.0, 2.0 * math.sqrt(e) - 1.0)
+
+    @property
+    def residual(self) -> int | None:
+        """The voxels the tool leaves behind: ``voxels - machinable``; None without reach."""
+        return None if self.machinable is None else self.voxels - self.machinable
+
+    def tool_faces(self, min_fraction: float = 1.0) -> tuple:
+        """The names of the faces from which the tool's centre reaches at least ``min_fraction`` of
+        the voxels in a straight line."""
+        if self.reachable is None:
+            raise ValueError("tool_faces: this instance carries no reach counts (extract_features(tool=...))")
+        return tuple(f for f, c in zip(FACES, self.reachable) if c >= min_fraction * self.voxels)
 
     def open_faces(self, min_fraction: float = 1.0) -> tuple:
         """The names of the faces toward which at least ``min_fraction`` of the voxels are open:
@@ -71,7 +121,9 @@ class FeatureInstance:
     def to_dict(self, min_fraction: float = 1.0) -> dict:
         """JSON-safe record; with access counts also ``access`` (face -> voxels), ``open_faces``
         (at ``min_fraction``), ``through`` and ``enclosed``; with dimensions also ``clearance2``,
-        ``clearance_at``, ``tool_diameter`` (None where it is unbounded) and ``wall_voxels``."""
+        ``clearance_at``, ``tool_diameter`` (None where it is unbounded) and ``wall_voxels``; with
+        reach also ``tool`` (need2, cut2), ``entry2`` and ``reachable`` (face -> value), ``tool_faces``
+        (at ``min_fraction``), ``unreachable``, ``machinable`` and ``residual``."""
         d = {"id": self.id, "class": self.cls, "voxels": self.voxels, "bbox": list(self.bbox),
              "centroid": list(self.centroid)}
         if self.access is not None:
@@ -81,16 +133,22 @@ class FeatureInstance:
             tool = self.tool_diameter
             d.update(clearance2=self.clearance2, clearance_at=list(self.clearance_at),
                      tool_diameter=tool if math.isfinite(tool) else None, wall_voxels=self.wall_voxels)
+        if self.reachable is not None:
+            d.update(tool=list(self.tool), entry2=dict(zip(FACES, self.entry2)),
+                     reachable=dict(zip(FACES, self.reachable)), tool_faces=list(self.tool_faces(min_fraction)),
+                     unreachable=self.unreachable, machinable=self.machinable, residual=self.residual)
         return d
 
     @staticmethod
-    def from_table(table, offsets, min_voxels: int = 1, access=None, dims=None,
-                   shape=None) -> "list[list[FeatureInstance]]":
+    def from_table(table, offsets, min_voxels: int = 1, access=None, dims=None, shape=None, reach=None,
+                   tool=None) -> "list[list[FeatureInstance]]":
         """Per-sample record lists from an instance table int64 ``[T, 13]`` and its ``offsets``
         ``[N + 1]`` (tensors or arrays).  Components of fewer than ``min_voxels`` voxels are left
         out; the others keep their ``id``.  ``access``: the access table int64 ``[T, 8]`` of the
         same rows, or None.  ``dims``: the dimension table int64 ``[T, 4]`` of the same rows, or None;
-        with it ``shape``, the ``(D, H, W)`` of a sample, which turns ``at`` into ``(z, y, x)``."""
+        with it ``shape``, the ``(D, H, W)`` of a sample, which turns ``at`` into ``(z, y, x)``.
+        ``reach``: the reach table int64 ``[T, 15]`` of the same rows, or None; with it ``tool``, the
+        ``(need2, cut2)`` it was made for."""
         tab = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.int64).reshape(-1, 13)
         off = np.asarray(offsets.cpu() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
         acc = None
@@ -106,6 +164,14 @@ class FeatureInstance:
             if shape is None or len(shape) != 3:
                 raise ValueError("from_table: dims needs shape = (D, H, W)")
             _, H, W = (int(s) for s in shape)
+        rch = None
+        if reach is not None:
+            rch = np.asarray(reach.cpu() if hasattr(reach, "cpu") else reach, dtype=np.int64).reshape(-1, 15)
+            if len(rch) != len(tab) or not np.array_equal(rch[:, 14], tab[:, 2]):
+                raise ValueError("from_table: the reach table does not belong to this instance table")
+            if tool is None or len(tool) != 2:
+                raise ValueError("from_table: reach needs tool = (need2, cut2)")
+            tool = (int(tool[0]), int(tool[1]))
         out = []
         for n in range(len(off) - 1):
             recs = []
@@ -124,6 +190,9 @@ class FeatureInstance:
                     r2, at, wall = (int(v) for v in dim[k, :3])
                     rec.clearance2, rec.wall_voxels = r2, wall
                     rec.clearance_at = (at // (H * W), at // W % H, at % W)
+                if rch is not None:
+                    rec.entry2, rec.reachable = tuple(int(v) for v in rch[k, :6]), tuple(int(v) for v in rch[k, 6:12])
+                    rec.unreachable, rec.machinable, rec.tool = int(rch[k, 12]), int(rch[k, 13]), tool
                 recs.append(rec)
             out.append(recs)
         return out
