@@ -281,7 +281,8 @@ def evaluate_segmentation(model, x, y, batch_size: int = 32, device=None, packed
 @torch.no_grad()
 def extract_features(model, x, batch_size: int = 32, device=None, packed_size: int | None = None,
                      background: int | None = 0, connectivity: int = 6, min_voxels: int = 1,
-                     return_ids: bool = False, access: bool = False, dimensions: bool = False, tool=None):
+                     return_ids: bool = False, access: bool = False, dimensions: bool = False, tool=None,
+                     contacts: bool = False):
     """The machining features of each part -> (one list of :class:`FeatureInstance` per sample,
     ids int32 [N, S, S, S] or None).
 
@@ -314,6 +315,14 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
     from the centres it reaches (``residual``: the rest); ``tool_faces()`` names the faces it can
     come from.  Runs on the model's device (``ops.reach``); 15 more integers per component cross
     to the host.
+
+    With ``contacts`` every record also says what the feature borders: ``wall_area``, ``open_area``
+    and ``shared_area`` are, per side ``+z, -z, +x, -x, +y, -y``, the faces of its voxels that meet
+    material (``x != 0``), free space or the outside of the grid, and another feature; ``neighbors``
+    lists ``(id, face, faces)`` for every feature of the same part it touches and the side on which
+    that one lies; ``surface``, ``floor(face)``, ``blind(face)`` and ``entered_through(face)`` follow
+    from these.  Runs on the model's device (``ops.contact``); 19 more integers per component and 4
+    per touching pair and side cross to the host.
     """
     from .utils.seginstances import FeatureInstance, tool_thresholds
 
@@ -338,11 +347,16 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
         xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
         table, offsets, idb, *more = model.instances(xb, background=background, connectivity=connectivity,
                                                      want_ids=return_ids, want_access=access, want_dims=dimensions,
-                                                     want_reach=thresholds)
+                                                     want_reach=thresholds, want_contacts=contacts)
+        pairs = None
+        if contacts:
+            *more, con, adj = more
+            pairs = (con, adj)
         feats += FeatureInstance.from_table(table, offsets, min_voxels, access=more[0] if access else None,
                                             dims=more[1 if access else 0] if dimensions else None,
                                             shape=tuple(xb.shape[1:4]),
-                                            reach=more[-1] if thresholds is not None else None, tool=thresholds)
+                                            reach=more[-1] if thresholds is not None else None, tool=thresholds,
+                                            contacts=pairs)
         if return_ids:
             ids.append(idb.cpu())
     if not return_ids:
@@ -353,7 +367,7 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
 
 @torch.no_grad()
 def label_components(labels, background: int | None = 0, connectivity: int = 6, device=None, occupancy=None,
-                     dimensions: bool = False, tool=None):
+                     dimensions: bool = False, tool=None, contacts: bool = False):
     """Connected components of label volumes the caller already has (ground truth, say) ->
     (ids int32 [N, D, H, W], one list of :class:`FeatureInstance` per sample).
 
@@ -363,9 +377,11 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     ``occupancy``, an integer or bool array of the labels' shape (material: non-zero), adds the
     access counts to the records as :func:`extract_features` does with ``access``; ``dimensions``
     (which needs ``occupancy``) adds the clear widths as its ``dimensions`` does, ``tool`` (a
-    diameter in voxels, which needs ``occupancy`` too) the reach of that tool as its ``tool`` does.
+    diameter in voxels, which needs ``occupancy`` too) the reach of that tool as its ``tool`` does,
+    ``contacts`` (which needs ``occupancy`` too) the wall, open and shared areas and the neighbours
+    as its ``contacts`` does.
     """
-    from .ops import access, ccl, edt, reach
+    from .ops import access, ccl, contact, edt, reach
     from .utils.seginstances import FeatureInstance, tool_thresholds
 
     if dimensions and occupancy is None:
@@ -373,6 +389,9 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
                          "measured against)")
     if tool is not None and occupancy is None:
         raise ValueError("label_components(): tool needs occupancy (the material the tool must clear)")
+    if contacts and occupancy is None:
+        raise ValueError("label_components(): contacts=True needs occupancy (the material that tells a wall from "
+                         "an opening)")
     thresholds = None if tool is None else tool_thresholds(tool)
 
     lt = torch.as_tensor(np.asarray(labels)) if not isinstance(labels, torch.Tensor) else labels
@@ -396,7 +415,7 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     lt = lt.to(device).to(torch.uint8).contiguous()
     roots, flags = ccl.connected_components(lt, background, connectivity, return_flags=True)
     ids, table, offsets = ccl.instance_table(lt, roots, want_ids=True, flags=flags)
-    acc = dim = rch = d2 = None
+    acc = dim = rch = d2 = pairs = None
     if ot is not None:
         occ = (ot.to(device) != 0).to(torch.uint8)
         acc, _ = access.access_table(ids, offsets, occ, rows=table.shape[0])
@@ -404,8 +423,11 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
             dim, d2 = edt.dimension_table(ids, offsets, occ, rows=table.shape[0], want_d2=thresholds is not None)
         if thresholds is not None:
             rch, _ = reach.reach_table(ids, offsets, occ, *thresholds, rows=table.shape[0], d2=d2)
+        if contacts:
+            pairs = contact.contact_table(ids, offsets, occ, rows=table.shape[0])
     return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets, access=acc, dims=dim,
-                                                         shape=tuple(lt.shape[1:]), reach=rch, tool=thresholds)
+                                                         shape=tuple(lt.shape[1:]), reach=rch, tool=thresholds,
+                                                         contacts=pairs)
 
 
 @torch.no_grad()

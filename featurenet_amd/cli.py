@@ -246,7 +246,8 @@ def cmd_features(a) -> int:
     feats, ids = api.extract_features(a.model, x, packed_size=a.packed_size,
                                       background=None if a.background < 0 else a.background,
                                       connectivity=a.connectivity, min_voxels=a.min_voxels, return_ids=bool(a.ids),
-                                      access=a.access, dimensions=a.dimensions, tool=a.tool)
+                                      access=a.access, dimensions=a.dimensions, tool=a.tool,
+                                      contacts=a.contacts)
     if a.ids:
         np.save(a.ids, ids)
     summary = json.dumps({"samples": [[f.to_dict(a.access_fraction) for f in fs] for fs in feats]})
@@ -553,6 +554,9 @@ def build_parser() -> argparse.ArgumentParser:
     ft.add_argument("--tool", type=float, default=None, metavar="T",
                     help="add the reach of a ball-shaped tool of diameter T voxels: entry2 and reachable per face, "
                          "tool_faces (at --access-fraction), unreachable, machinable, residual")
+    ft.add_argument("--contacts", action="store_true",
+                    help="add what each feature borders: wall_area, open_area, shared_area and floor per face, surface, "
+                         "neighbors (id, face, faces)")
     ft.set_defaults(fn=cmd_features)
 
     rc = sub.add_parser("reach", help="directional clearance: the squared clearance of the largest ball that reaches "

@@ -63,6 +63,9 @@ void fn_reach_chunk(int*);
 int fn_reach_scan(const void*, void*, int, int, int, int, hipStream_t);
 int fn_reach_stats(const void*, const void*, const void*, const void*, void*, int, int, int, int, long long, int, int,
                    hipStream_t);
+void fn_contact_chunk(int*);
+int fn_contact_stats(const void*, const void*, const void*, void*, void*, void*, void*, int, int, int, int, long long,
+                     long long, long long, hipStream_t);
 int fn_pw_wgrad(const void*, const void*, float*, long long, int, int, hipStream_t, const float*, const float*, int,
                 float*);
 int fn_pw_wgrad_blocks(long long, int, int);
@@ -852,6 +855,34 @@ PYBIND11_MODULE(_C, m) {
         "reach_stats");
   }, py::arg("ids"), py::arg("offsets"), py::arg("r6"), py::arg("dc2"), py::arg("raw"), py::arg("N"), py::arg("D"),
      py::arg("H"), py::arg("W"), py::arg("T"), py::arg("need2"), py::arg("cut2"), py::arg("st"), py::arg("ext"));
+  // contacts of feature instances (contact.hip): ids int32 [N*V] and offsets int64 [N+1] as for access_stats, occ
+  // uint8 [N*V] (material: != 0); contact int64 [T][19]: the faces of the row's voxels toward +z -z +x -x +y -y that
+  // meet material (0..5), free space or the outside of the grid (6..11), another instance (12..17), its voxels (18);
+  // keys uint64 [cap] / counts int64 [cap] / lost int64 [1]: the pair table of overlap_pairs under the key row_a <<
+  // 33 | row_b << 3 | face (1-based rows, row_a < row_b; T < 2^30), counts in faces; contact, keys, counts and lost
+  // are zero on entry; ext = {numel(ids), numel(occ), numel(offsets), numel(contact), numel(keys), numel(counts),
+  // numel(lost)}
+  m.def("contact_chunk", []() {
+    int t[2];
+    fn_contact_chunk(t);
+    return py::make_tuple(t[0], t[1]);
+  });
+  m.def("contact_stats", [](uintptr_t ids, uintptr_t occ, uintptr_t offsets, uintptr_t contact, uintptr_t keys,
+                            uintptr_t counts, uintptr_t lost, int N, int D, int H, int W, long long T, long long cap,
+                            long long probe, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "contact_stats", "ids");
+    fits(ext, 1, prod({N, D, H, W}), "contact_stats", "occ");
+    fits(ext, 2, N < 0 ? -1 : N + 1LL, "contact_stats", "offsets");
+    fits(ext, 3, prod({T, 19}), "contact_stats", "contact");
+    fits(ext, 4, cap, "contact_stats", "keys");
+    fits(ext, 5, cap, "contact_stats", "counts");
+    fits(ext, 6, 1, "contact_stats", "lost");
+    chk(fn_contact_stats(P<const void*>(ids), P<const void*>(occ), P<const void*>(offsets), P<void*>(contact),
+                         P<void*>(keys), P<void*>(counts), P<void*>(lost), N, D, H, W, T, cap, probe, S(st)),
+        "contact_stats");
+  }, py::arg("ids"), py::arg("occ"), py::arg("offsets"), py::arg("contact"), py::arg("keys"), py::arg("counts"),
+     py::arg("lost"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("T"), py::arg("cap"),
+     py::arg("probe"), py::arg("st"), py::arg("ext"));
   // multi-feature parts from their parameter tables (partgen.hip): params int32 [N][K][16]; occ / labels / slots
   // uint8 [N][S][S][S] (8-byte aligned) and packed uint8 [N][S^3/8], each 0 = not wanted; S % 8 == 0, 8 <= S <=
   // 256, K <= 32; ext = {numel(params), numel(occ), numel(packed), numel(labels), numel(slots)}

@@ -9,51 +9,14 @@
 // an open-addressing hash table keys uint64 [cap] (0 = empty) / counts int64 [cap], cap a power of
 // two, which the caller has zeroed: the SET of (key, count) pairs in it is exact and does not
 // depend on the order of the atomics; their slots do, so the caller sorts the occupied ones.
-#include "instance_pass.h"
-
-constexpr int OVL_LPROBE = 8;                   // LDS slots an update tries before it goes to global memory
-
-// The 64-bit finalizer of MurmurHash3: every output bit depends on every key bit.  The top 9 bits
-// pick the LDS slot, the low bits (cap <= 2^32) the global one.  A single multiplication is not
-// enough: the keys are pairs of small, correlated row numbers (rb = ra + d for a prediction close
-// to the truth), and its middle bits put them in clusters -- 12 probes per insert at load 0.4
-// where this gives 0.35, as random keys do.
-__device__ __forceinline__ unsigned long long ovl_mix(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
-
-// counts[slot of key] += cnt.  Linear probing from the key's home slot, at most `bound` (<= cap)
-// slots: a returning compare-and-swap claims an empty slot or shows whose it is.  An update that
-// finds neither its key nor an empty slot within the bound is dropped and its voxels counted in
-// lost[0] (the caller grows the table and runs again).  Nothing here waits for another thread.
-__device__ __forceinline__ void ovl_global_add(unsigned long long* keys, long long* counts, long long* lost,
-                                               unsigned long long mask, long long bound, unsigned long long key,
-                                               long long cnt) {
-  unsigned long long h = ovl_mix(key) & mask;
-  for (long long i = 0; i < bound; ++i) {
-    unsigned long long held = 0;
-    __hip_atomic_compare_exchange_strong(&keys[h], &held, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_AGENT);
-    if (held == 0 || held == key) {              // (held keeps 0 when the exchange was made)
-      __hip_atomic_fetch_add(&counts[h], cnt, IP_RLX_AGENT);
-      return;
-    }
-    h = (h + 1) & mask;
-  }
-  __hip_atomic_fetch_add(lost, cnt, IP_RLX_AGENT);
-}
+#include "pair_table.h"
 
 // The instance pass of instance_pass.h with a 64-bit key for the row number: a run of equal keys
 // along a row of W is one update of `len` voxels, so two solid volumes make one global update per
 // workgroup, not one per voxel.  The LDS table holds (key, count) and is entered at the key's hash,
-// not direct-mapped: an update goes to the global table only when the OVL_LPROBE slots from its
+// not direct-mapped: an update goes to the global table only when the PT_LPROBE slots from its
 // hash on are all held by other keys.  That costs the wave a returning global atomic inside the
-// loop, which a strictly direct-mapped table (OVL_LPROBE = 1) pays on most rows already at ~130
+// loop, which a strictly direct-mapped table (PT_LPROBE = 1) pays on most rows already at ~130
 // keys per chunk (59 against 46 us on the blobs of profiles/feature_match.md).
 __global__ __launch_bounds__(IP_NTHR) void overlap_pairs_kernel(const int* __restrict__ ids_a,
                                                                 const int* __restrict__ ids_b,
@@ -76,21 +39,21 @@ __global__ __launch_bounds__(IP_NTHR) void overlap_pairs_kernel(const int* __res
     const unsigned long long ra = (unsigned long long)(off_a[n] + a), rb = (unsigned long long)(off_b[n] + b);
     const unsigned long long key = on ? (ra << 32) | (rb & 0xffffffffull) : 0ull;
     const IpRun run = ip_run(key, x == 0);
-    if (run.head && key != 0) {
-      int slot = (int)(ovl_mix(key) >> 55) & (IP_SLOTS - 1);
+    if (run.head && key != 0) {                  // (pt_stage_add, spelt out: see pair_table.h)
+      int slot = (int)(pt_mix(key) >> 55) & (IP_SLOTS - 1);
       bool met = false;
-      for (int p = 0; p < OVL_LPROBE && !met; ++p) {
+      for (int p = 0; p < PT_LPROBE && !met; ++p) {
         const unsigned long long held = atomicCAS(&s_key[slot], 0ull, key);
         met = held == 0 || held == key;
         if (met) atomicAdd(&s_cnt[slot], (unsigned long long)run.len);
         slot = (slot + 1) & (IP_SLOTS - 1);
       }
-      if (!met) ovl_global_add(keys, counts, lost, mask, bound, key, run.len);
+      if (!met) pt_global_add(keys, counts, lost, mask, bound, key, run.len);
     }
   }
   __syncthreads();
   for (int s = tid; s < IP_SLOTS; s += IP_NTHR)
-    if (s_key[s] != 0) ovl_global_add(keys, counts, lost, mask, bound, s_key[s], (long long)s_cnt[s]);
+    if (s_key[s] != 0) pt_global_add(keys, counts, lost, mask, bound, s_key[s], (long long)s_cnt[s]);
 }
 
 extern "C" void fn_overlap_chunk(int* t) { t[0] = IP_CHUNK, t[1] = IP_SLOTS; }

@@ -261,7 +261,7 @@ class FeatureNet3DSeg(nn.Module):
     @torch.no_grad()
     def instances(self, x: torch.Tensor, background: int | None = 0, connectivity: int = 6,
                   want_ids: bool = False, want_access: bool = False, want_dims: bool = False,
-                  want_reach: tuple | None = None):
+                  want_reach: tuple | None = None, want_contacts: bool = False):
         """The features in each sample: :meth:`predict`'s labels split into connected components
         -> ``(table, offsets, ids or None)`` on the model's device.  ``table`` int64 ``[T, 13]``
         has one row per component (``sample, class, voxels, root, z0, y0, x0, z1, y1, x1, sum_z,
@@ -285,14 +285,20 @@ class FeatureNet3DSeg(nn.Module):
         the largest squared clearance of a straight path from each face to one of the component's
         voxels, the voxels the tool's centre reaches from each face and from none, the voxels the
         tool clears, and all of them (``ops.reach``).  It shares the distance transform of
-        ``want_dims``."""
-        from ..ops import access, ccl, edt, reach
+        ``want_dims``.
+
+        With ``want_contacts`` ``contact`` int64 ``[T, 19]`` and ``adj`` int64 ``[P, 4]`` are appended
+        (after ``acc``, ``dim`` and ``reach``): row by row of ``table`` the voxel faces toward each
+        side that meet material (``x != 0``), free space or the outside of the grid, and another
+        component, and the voxels; and one row ``(row_a, row_b, face, faces)`` per pair of components
+        ``row_a < row_b`` and side of ``a`` on which they share faces (``ops.contact``)."""
+        from ..ops import access, ccl, contact, edt, reach
 
         if connectivity not in (6, 26):
             raise ValueError(f"instances: connectivity must be 6 or 26, not {connectivity!r}")
         labels = self.predict(x)
         roots, flags = ccl.connected_components(labels, background, connectivity, return_flags=True)
-        more = want_access or want_dims or want_reach is not None
+        more = want_access or want_dims or want_reach is not None or want_contacts
         ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids or more, flags=flags)
         if not more:
             return table, offsets, ids
@@ -310,6 +316,8 @@ class FeatureNet3DSeg(nn.Module):
         if want_reach is not None:
             need2, cut2 = want_reach
             out.append(reach.reach_table(ids, offsets, occ, need2, cut2, rows=table.shape[0], d2=d2)[0])
+        if want_contacts:
+            out.extend(contact.contact_table(ids, offsets, occ, rows=table.shape[0]))
         return tuple(out)
 
     def match(self, x: torch.Tensor, y: torch.Tensor, background: int | None = 0, connectivity: int = 6):

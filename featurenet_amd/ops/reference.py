@@ -441,6 +441,72 @@ def reach_table(ids: torch.Tensor, offsets: torch.Tensor, r6: torch.Tensor, dc2:
     return out
 
 
+CONTACT_NCOL = 19          # wall, open and shared faces toward the six sides, voxels
+CONTACT_MAX_T = 1 << 30    # rows a pair key of the contact kernel holds (two rows and a face in 63 bits)
+
+
+def contact_table(ids: torch.Tensor, offsets: torch.Tensor, occ: torch.Tensor):
+    """Contact table of an instance-id volume over an occupancy volume -> ``(contact, adj)``.
+
+    ``ids`` int32 ``[N, D, H, W]`` and ``offsets`` int64 ``[N + 1]`` as :func:`instance_table`
+    gives them (``T = offsets[-1]``), ``occ`` uint8 of the ids' shape (material: ``occ != 0``).  For
+    a voxel ``v`` with ``ids[v] > 0`` and a face ``k`` of ``+z, -z, +x, -x, +y, -y`` let ``u`` be its
+    neighbour toward that face in the same sample.  The face of ``v`` is *interior* when ``u`` lies
+    in the grid and carries the same id; a *wall* when ``u`` lies in the grid, carries no id
+    (``ids[u] <= 0``) and is material; *open* when ``u`` lies outside the grid, or carries no id and
+    is not material; *shared* when ``u`` lies in the grid and carries another id ``> 0``.  The
+    voxel's own occupancy does not enter.
+
+    ``contact`` int64 ``[T, 19]``: row ``offsets[n] + id - 1`` counts, of id ``id`` of sample ``n``,
+    the wall faces toward each side (columns 0..5), the open faces (6..11), the shared faces
+    (12..17) and the voxels (18); a voxel with id 0 or whose row lies outside the table counts
+    nowhere, a row that no voxel carries is 0.  ``adj`` int64 ``[P, 4]``: one row ``(row_a, row_b, k,
+    faces)`` per triple that occurs, 0-based table rows with ``row_a < row_b``, sorted by ``(row_a,
+    row_b, k)``: ``faces`` faces of ``a`` have their neighbour toward side ``k`` in ``b`` (each
+    shared face is told once, from its lower row; a neighbour whose row lies outside the table is
+    *shared* in ``contact`` and has no row in ``adj``).  Shifted views, ``bincount`` and
+    ``torch.unique``: the oracle of ``contact_stats`` and the CPU path of
+    ``ops.contact.contact_table``."""
+    N, D, H, W = ids.shape
+    dev = ids.device
+    T = int(offsets[-1])
+    contact = torch.zeros(T, CONTACT_NCOL, dtype=torch.int64, device=dev)
+    adj = torch.zeros(0, 4, dtype=torch.int64, device=dev)
+    if T == 0 or ids.numel() == 0:
+        return contact, adj
+    if T >= CONTACT_MAX_T:
+        raise ValueError(f"contact_table: the instance table must have fewer than 2^30 rows, not {T}")
+    own = ids.to(torch.int64)
+    base = offsets.to(torch.int64)[:-1].view(N, 1, 1, 1) - 1
+    row = own + base                                                # 0-based
+    live = (own > 0) & (row >= 0) & (row < T)
+    material = occ != 0
+    keys = []
+    for k, (axis, toward) in enumerate(((1, 1), (1, -1), (3, 1), (3, -1), (2, 1), (2, -1))):
+        L = ids.shape[axis]
+        inside = torch.zeros(ids.shape, dtype=torch.bool, device=dev)
+        other = torch.zeros_like(own)
+        solid = torch.zeros_like(inside)
+        if L > 1:                                # the voxels that have a neighbour on that side, and it
+            here, there = (0, 1) if toward > 0 else (1, 0)
+            inside.narrow(axis, here, L - 1).fill_(True)
+            other.narrow(axis, here, L - 1).copy_(own.narrow(axis, there, L - 1))
+            solid.narrow(axis, here, L - 1).copy_(material.narrow(axis, there, L - 1))
+        named = inside & (other > 0)
+        shared = named & (other != own)
+        bare = inside & ~named
+        for c, m in enumerate((bare & solid, ~inside | (bare & ~solid), shared)):
+            contact[:, 6 * c + k] = torch.bincount(row[live & m], minlength=T)
+        mate = other + base
+        tell = live & shared & (mate < T) & (row < mate)
+        keys.append((row[tell] << 33) | (mate[tell] << 3) | k)
+    contact[:, 18] = torch.bincount(row[live], minlength=T)
+    key, faces = torch.unique(torch.cat(keys), return_counts=True)
+    if key.numel():
+        adj = torch.stack([key >> 33, (key >> 3) & (CONTACT_MAX_T - 1), key & 7, faces], 1)
+    return contact, adj
+
+
 def _part_volume(cls: int, f: dict, X, Y, Z, top: int):
     """The volume of one feature class over canonical quarter-voxel coordinates ``X, Y, Z``
     (int64 ``[n, S, S, S]``); ``f`` maps the field names of a table row to ``[n, 1, 1, 1]``."""

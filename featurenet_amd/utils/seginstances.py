@@ -4,7 +4,9 @@ One :class:`FeatureInstance` per row of the instance table (``ops.ccl.instance_t
 integer counts and bounds, the centroid as ``sum / voxels`` in float64 on the host; with an access
 table (``ops.access.access_table``) also the voxels open toward each face of the grid; with a dimension table (``ops.edt.dimension_table``) also its clear width: the
 largest squared distance from one of its voxels to the material, and where that voxel lies; with a
-reach table (``ops.reach.reach_table``) also what a given tool reaches from each face and clears.
+reach table (``ops.reach.reach_table``) also what a given tool reaches from each face and clears; with
+the contact tables (``ops.contact.contact_table``) also the area of its walls, of its openings and of
+the faces it shares with other instances, side by side, and which instances those are.
 """
 from __future__ import annotations
 
@@ -59,6 +61,10 @@ class FeatureInstance:
     unreachable: int | None = None      # its voxels the tool's centre reaches from no face
     machinable: int | None = None       # its voxels the tool removes from the centres it reaches
     tool: tuple | None = None      # (need2, cut2) of the tool these counts were made for
+    wall_area: tuple | None = None      # per side, in FACES order, its voxel faces that meet material
+    open_area: tuple | None = None      # per side, its voxel faces that meet free space or the outside of the grid
+    shared_area: tuple | None = None    # per side, its voxel faces that meet another instance
+    neighbors: tuple | None = None      # (id, face, faces): instance ``id`` of the sample lies toward ``face`` on ``faces`` faces
 
     @property
     def clearance(self) -> float | None:
@@ -98,6 +104,35 @@ class FeatureInstance:
             raise ValueError("tool_faces: this instance carries no reach counts (extract_features(tool=...))")
         return tuple(f for f, c in zip(FACES, self.reachable) if c >= min_fraction * self.voxels)
 
+    @property
+    def surface(self) -> int | None:
+        """The faces of its voxels that are not interior: wall, open and shared, over all sides; None
+        without contacts."""
+        if self.wall_area is None:
+            return None
+        return sum(self.wall_area) + sum(self.open_area) + sum(self.shared_area)
+
+    def floor(self, face: str) -> int:
+        """The wall area on the side opposite ``face``: what a tool that enters through ``face`` finds
+        at the bottom (0 for a hole that goes through)."""
+        if face not in FACES:
+            raise ValueError(f"floor: face must be one of {FACES}, not {face!r}")
+        if self.wall_area is None:
+            raise ValueError("floor: this instance carries no contact areas (extract_features(contacts=True))")
+        return self.wall_area[FACES.index(face) ^ 1]
+
+    def blind(self, face: str) -> bool:
+        """Entered through ``face`` it has a floor: ``floor(face) > 0``."""
+        return self.floor(face) > 0
+
+    def entered_through(self, face: str) -> tuple:
+        """The ids of the instances of the same sample that lie toward ``face`` of this one."""
+        if face not in FACES:
+            raise ValueError(f"entered_through: face must be one of {FACES}, not {face!r}")
+        if self.neighbors is None:
+            raise ValueError("entered_through: this instance carries no contacts (extract_features(contacts=True))")
+        return tuple(i for i, f, _ in self.neighbors if f == face)
+
     def open_faces(self, min_fraction: float = 1.0) -> tuple:
         """The names of the faces toward which at least ``min_fraction`` of the voxels are open:
         no material lies between such a voxel and that face of the grid."""
@@ -123,7 +158,9 @@ class FeatureInstance:
         (at ``min_fraction``), ``through`` and ``enclosed``; with dimensions also ``clearance2``,
         ``clearance_at``, ``tool_diameter`` (None where it is unbounded) and ``wall_voxels``; with
         reach also ``tool`` (need2, cut2), ``entry2`` and ``reachable`` (face -> value), ``tool_faces``
-        (at ``min_fraction``), ``unreachable``, ``machinable`` and ``residual``."""
+        (at ``min_fraction``), ``unreachable``, ``machinable`` and ``residual``; with contacts also
+        ``wall_area``, ``open_area``, ``shared_area`` and ``floor`` (face -> faces), ``surface`` and
+        ``neighbors`` (a list of ``{"id", "face", "faces"}``)."""
         d = {"id": self.id, "class": self.cls, "voxels": self.voxels, "bbox": list(self.bbox),
              "centroid": list(self.centroid)}
         if self.access is not None:
@@ -137,18 +174,25 @@ class FeatureInstance:
             d.update(tool=list(self.tool), entry2=dict(zip(FACES, self.entry2)),
                      reachable=dict(zip(FACES, self.reachable)), tool_faces=list(self.tool_faces(min_fraction)),
                      unreachable=self.unreachable, machinable=self.machinable, residual=self.residual)
+        if self.wall_area is not None:
+            d.update(wall_area=dict(zip(FACES, self.wall_area)), open_area=dict(zip(FACES, self.open_area)),
+                     shared_area=dict(zip(FACES, self.shared_area)), floor={f: self.floor(f) for f in FACES},
+                     surface=self.surface,
+                     neighbors=[{"id": i, "face": f, "faces": c} for i, f, c in self.neighbors])
         return d
 
     @staticmethod
     def from_table(table, offsets, min_voxels: int = 1, access=None, dims=None, shape=None, reach=None,
-                   tool=None) -> "list[list[FeatureInstance]]":
+                   tool=None, contacts=None) -> "list[list[FeatureInstance]]":
         """Per-sample record lists from an instance table int64 ``[T, 13]`` and its ``offsets``
         ``[N + 1]`` (tensors or arrays).  Components of fewer than ``min_voxels`` voxels are left
         out; the others keep their ``id``.  ``access``: the access table int64 ``[T, 8]`` of the
         same rows, or None.  ``dims``: the dimension table int64 ``[T, 4]`` of the same rows, or None;
         with it ``shape``, the ``(D, H, W)`` of a sample, which turns ``at`` into ``(z, y, x)``.
         ``reach``: the reach table int64 ``[T, 15]`` of the same rows, or None; with it ``tool``, the
-        ``(need2, cut2)`` it was made for."""
+        ``(need2, cut2)`` it was made for.  ``contacts``: ``(contact, adj)``, the contact table int64
+        ``[T, 19]`` of the same rows and its pair list int64 ``[P, 4]``, or None; a neighbour that
+        ``min_voxels`` leaves out of the lists still appears in ``neighbors``, by its id."""
         tab = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.int64).reshape(-1, 13)
         off = np.asarray(offsets.cpu() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
         acc = None
@@ -172,6 +216,20 @@ class FeatureInstance:
             if tool is None or len(tool) != 2:
                 raise ValueError("from_table: reach needs tool = (need2, cut2)")
             tool = (int(tool[0]), int(tool[1]))
+        con = near = None
+        if contacts is not None:
+            con, adj = (np.asarray(t.cpu() if hasattr(t, "cpu") else t, dtype=np.int64) for t in contacts)
+            con, adj = con.reshape(-1, 19), adj.reshape(-1, 4)
+            if len(con) != len(tab) or not np.array_equal(con[:, 18], tab[:, 2]):
+                raise ValueError("from_table: the contact table does not belong to this instance table")
+            if len(adj) and (adj[:, :2].min() < 0 or adj[:, :2].max() >= len(tab) or adj[:, 2].min() < 0
+                             or adj[:, 2].max() > 5):
+                raise ValueError("from_table: the contact pairs do not belong to this instance table")
+            first = off[np.searchsorted(off, np.arange(len(tab)), side="right") - 1]    # the first row of each row's sample
+            near = [[] for _ in range(len(tab))]
+            for a, b, k, faces in adj.tolist():      # a sees b toward k, b sees a toward the opposite side
+                near[a].append((b - int(first[b]) + 1, k, faces))
+                near[b].append((a - int(first[a]) + 1, k ^ 1, faces))
         out = []
         for n in range(len(off) - 1):
             recs = []
@@ -193,6 +251,10 @@ class FeatureInstance:
                 if rch is not None:
                     rec.entry2, rec.reachable = tuple(int(v) for v in rch[k, :6]), tuple(int(v) for v in rch[k, 6:12])
                     rec.unreachable, rec.machinable, rec.tool = int(rch[k, 12]), int(rch[k, 13]), tool
+                if con is not None:
+                    rec.wall_area, rec.open_area = tuple(int(v) for v in con[k, :6]), tuple(int(v) for v in con[k, 6:12])
+                    rec.shared_area = tuple(int(v) for v in con[k, 12:18])
+                    rec.neighbors = tuple((i, FACES[f], c) for i, f, c in sorted(near[k]))
                 recs.append(rec)
             out.append(recs)
         return out
