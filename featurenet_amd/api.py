@@ -282,7 +282,7 @@ def evaluate_segmentation(model, x, y, batch_size: int = 32, device=None, packed
 def extract_features(model, x, batch_size: int = 32, device=None, packed_size: int | None = None,
                      background: int | None = 0, connectivity: int = 6, min_voxels: int = 1,
                      return_ids: bool = False, access: bool = False, dimensions: bool = False, tool=None,
-                     contacts: bool = False):
+                     contacts: bool = False, walls=False):
     """The machining features of each part -> (one list of :class:`FeatureInstance` per sample,
     ids int32 [N, S, S, S] or None).
 
@@ -323,10 +323,21 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
     that one lies; ``surface``, ``floor(face)``, ``blind(face)`` and ``entered_through(face)`` follow
     from these.  Runs on the model's device (``ops.contact``); 19 more integers per component and 4
     per touching pair and side cross to the host.
+
+    With ``walls`` -- True, or a wall thickness ``t`` in voxels -- every record also says how close
+    the feature comes to another one of its part without touching it: ``gap2`` is the smallest
+    squared distance from one of its voxels to a voxel of another feature, ``gap_at`` the first voxel
+    that attains it, ``gap_to`` the id of the feature nearest to that voxel, and ``gap`` and
+    ``min_wall`` (the wall left between the two, in voxels: ``max(0, gap - 1)``) follow from these;
+    all are None for a feature alone in its part.  With a thickness, ``thin_voxels`` counts its voxels
+    that have another feature behind a wall of at most ``t`` voxels.  The labelled distance
+    transform runs on the model's device (``ops.nearest``); 5 more integers per component cross to
+    the host.
     """
     from .utils.seginstances import FeatureInstance, tool_thresholds
 
     thresholds = None if tool is None else tool_thresholds(tool)
+    limit2 = _wall_limit(walls)
     if isinstance(model, (str, Path)):
         model, _ = load(model, device)
     if not isinstance(model, FeatureNet3DSeg):
@@ -347,7 +358,11 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
         xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
         table, offsets, idb, *more = model.instances(xb, background=background, connectivity=connectivity,
                                                      want_ids=return_ids, want_access=access, want_dims=dimensions,
-                                                     want_reach=thresholds, want_contacts=contacts)
+                                                     want_reach=thresholds, want_contacts=contacts,
+                                                     want_walls=limit2)
+        wall = None
+        if limit2 is not None:
+            *more, wall = more
         pairs = None
         if contacts:
             *more, con, adj = more
@@ -356,7 +371,7 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
                                             dims=more[1 if access else 0] if dimensions else None,
                                             shape=tuple(xb.shape[1:4]),
                                             reach=more[-1] if thresholds is not None else None, tool=thresholds,
-                                            contacts=pairs)
+                                            contacts=pairs, walls=wall, thin=walls is not True)
         if return_ids:
             ids.append(idb.cpu())
     if not return_ids:
@@ -367,7 +382,7 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
 
 @torch.no_grad()
 def label_components(labels, background: int | None = 0, connectivity: int = 6, device=None, occupancy=None,
-                     dimensions: bool = False, tool=None, contacts: bool = False):
+                     dimensions: bool = False, tool=None, contacts: bool = False, walls=False):
     """Connected components of label volumes the caller already has (ground truth, say) ->
     (ids int32 [N, D, H, W], one list of :class:`FeatureInstance` per sample).
 
@@ -379,9 +394,10 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     (which needs ``occupancy``) adds the clear widths as its ``dimensions`` does, ``tool`` (a
     diameter in voxels, which needs ``occupancy`` too) the reach of that tool as its ``tool`` does,
     ``contacts`` (which needs ``occupancy`` too) the wall, open and shared areas and the neighbours
-    as its ``contacts`` does.
+    as its ``contacts`` does, ``walls`` (True or a wall thickness in voxels; it needs no
+    ``occupancy``) the gap to the nearest other feature as its ``walls`` does.
     """
-    from .ops import access, ccl, contact, edt, reach
+    from .ops import access, ccl, contact, edt, nearest, reach
     from .utils.seginstances import FeatureInstance, tool_thresholds
 
     if dimensions and occupancy is None:
@@ -393,6 +409,7 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
         raise ValueError("label_components(): contacts=True needs occupancy (the material that tells a wall from "
                          "an opening)")
     thresholds = None if tool is None else tool_thresholds(tool)
+    limit2 = _wall_limit(walls)
 
     lt = torch.as_tensor(np.asarray(labels)) if not isinstance(labels, torch.Tensor) else labels
     if lt.is_floating_point() or lt.dtype == torch.bool:
@@ -415,7 +432,7 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     lt = lt.to(device).to(torch.uint8).contiguous()
     roots, flags = ccl.connected_components(lt, background, connectivity, return_flags=True)
     ids, table, offsets = ccl.instance_table(lt, roots, want_ids=True, flags=flags)
-    acc = dim = rch = d2 = pairs = None
+    acc = dim = rch = d2 = pairs = wall = None
     if ot is not None:
         occ = (ot.to(device) != 0).to(torch.uint8)
         acc, _ = access.access_table(ids, offsets, occ, rows=table.shape[0])
@@ -425,9 +442,50 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
             rch, _ = reach.reach_table(ids, offsets, occ, *thresholds, rows=table.shape[0], d2=d2)
         if contacts:
             pairs = contact.contact_table(ids, offsets, occ, rows=table.shape[0])
+    if limit2 is not None:
+        wall, _ = nearest.wall_table(ids, offsets, limit2, rows=table.shape[0])
     return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets, access=acc, dims=dim,
                                                          shape=tuple(lt.shape[1:]), reach=rch, tool=thresholds,
-                                                         contacts=pairs)
+                                                         contacts=pairs, walls=wall, thin=walls is not True)
+
+
+def _wall_limit(walls):
+    """``limit2`` of the ``walls`` option: None when off, 0 for True (no thin count is reported),
+    else ``wall_threshold`` of the thickness."""
+    from .utils.seginstances import wall_threshold
+
+    if walls is None or walls is False:
+        return None
+    return 0 if walls is True else wall_threshold(walls)
+
+
+@torch.no_grad()
+def nearest_instances(ids, device=None):
+    """Labelled distance transform -> ``(d2, nearest)``, both int32 ``[N, 2, D, H, W]`` (or ``[2, D, H,
+    W]`` for one ``[D, H, W]`` volume).  A voxel of ``ids`` (an integer array) with a value ``> 0``
+    belongs to the instance of that number (up to ``2^31 - 1``); for every voxel ``nearest[:, 0]`` is
+    the id of the nearest instance of its sample (the smallest among equally near ones) and ``d2[:,
+    0]`` the squared distance to it, 0 and its own id on an instance's voxel; ``nearest[:, 1]`` and
+    ``d2[:, 1]`` are the same for the nearest OTHER instance.  A missing one (no instance, or a single
+    one, in the sample) is id 0 at :data:`EDT_INF`.  Each axis is at most 128 long.  ``device``
+    defaults to the GPU when there is one (the ``nearest`` kernels), else the CPU reference path; the
+    result is the same.
+    """
+    from .ops import nearest
+
+    it = torch.as_tensor(np.asarray(ids)) if not isinstance(ids, torch.Tensor) else ids
+    if it.is_floating_point() or it.is_complex() or it.dtype == torch.bool:
+        raise ValueError(f"nearest_instances(): ids must be integers, not {it.dtype}")
+    if it.dim() not in (3, 4):
+        raise ValueError(f"nearest_instances(): ids must be [D, H, W] or [N, D, H, W], not {tuple(it.shape)}")
+    if it.dtype != torch.int32 and it.numel() and int(it.max()) >= 1 << 31:
+        raise ValueError("nearest_instances(): ids must be below 2^31")
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    it = it.clamp(min=0).to(torch.int32).to(device)
+    nn = nearest.nearest_labels(it if it.dim() == 4 else it[None])
+    nn = (nn if it.dim() == 4 else nn[0]).cpu()
+    return (nn >> 32).to(torch.int32).numpy(), (nn & 0xFFFFFFFF).to(torch.int32).numpy()
 
 
 @torch.no_grad()

@@ -247,7 +247,7 @@ def cmd_features(a) -> int:
                                       background=None if a.background < 0 else a.background,
                                       connectivity=a.connectivity, min_voxels=a.min_voxels, return_ids=bool(a.ids),
                                       access=a.access, dimensions=a.dimensions, tool=a.tool,
-                                      contacts=a.contacts)
+                                      contacts=a.contacts, walls=False if a.walls is None else a.walls)
     if a.ids:
         np.save(a.ids, ids)
     summary = json.dumps({"samples": [[f.to_dict(a.access_fraction) for f in fs] for fs in feats]})
@@ -270,6 +270,26 @@ def cmd_distance(a) -> int:
     summary = json.dumps({"shape": list(d2.shape), "seeds": int((d2 == 0).sum()),
                           "max_distance_sq": int(finite.max()) if finite.size else None,
                           "unreached_voxels": int((d2 >= api.EDT_INF).sum())})
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(summary + "\n")
+    print(summary)
+    return 0
+
+
+def cmd_nearest(a) -> int:
+    import numpy as np
+
+    from . import api
+
+    ids = np.load(a.input, allow_pickle=False)
+    d2, nearest = api.nearest_instances(ids, device=a.device or None)
+    np.savez(a.output, d2=d2, nearest=nearest)
+    other = np.moveaxis(d2, -4, 0)[1]
+    on = other[(ids > 0) & (other < api.EDT_INF)]
+    summary = json.dumps({"shape": list(d2.shape), "instance_voxels": int((ids > 0).sum()),
+                          "min_gap_sq": int(on.min()) if on.size else None,
+                          "voxels_without_other": int((other >= api.EDT_INF).sum())})
     if a.json:
         with open(a.json, "w") as f:
             f.write(summary + "\n")
@@ -557,7 +577,21 @@ def build_parser() -> argparse.ArgumentParser:
     ft.add_argument("--contacts", action="store_true",
                     help="add what each feature borders: wall_area, open_area, shared_area and floor per face, surface, "
                          "neighbors (id, face, faces)")
+    ft.add_argument("--walls", type=float, nargs="?", const=True, default=None, metavar="T",
+                    help="add the gap to the nearest other feature of the part: gap2, gap_at, gap_to, min_wall; with T "
+                         "also thin_voxels, the voxels with another feature behind a wall of at most T voxels")
     ft.set_defaults(fn=cmd_features)
+
+    nr = sub.add_parser("nearest", help="labelled distance transform: the nearest and the nearest other instance of "
+                                        "every voxel with their squared distances -> .npz (d2, nearest)")
+    nr.add_argument("input", help="[D, H, W] or [N, D, H, W] integer instance ids (.npy), > 0 = an instance's voxel, "
+                                  "each axis at most 128")
+    nr.add_argument("-o", "--output", required=True,
+                    help="d2 and nearest, int32 [2, D, H, W] or [N, 2, D, H, W]: rank 0 the nearest instance, rank 1 "
+                         "the nearest other one (.npz)")
+    nr.add_argument("--device", default="", help="cuda / cpu (default: the GPU when there is one)")
+    nr.add_argument("--json", default="", metavar="OUT", help="also write the summary to this file")
+    nr.set_defaults(fn=cmd_nearest)
 
     rc = sub.add_parser("reach", help="directional clearance: the squared clearance of the largest ball that reaches "
                                       "each voxel in a straight line from each face -> int32 .npy")

@@ -59,6 +59,9 @@ int fn_access_stats(const void*, const void*, const void*, const void*, const vo
 void fn_edt_chunk(int*);
 int fn_edt_transform(const void*, void*, void*, int, int, int, int, int, int, hipStream_t);
 int fn_edt_stats(const void*, const void*, const void*, void*, int, int, int, int, long long, hipStream_t);
+void fn_nn_chunk(int*);
+int fn_nn_transform(const void*, void*, void*, int, int, int, int, int, hipStream_t);
+int fn_wall_stats(const void*, const void*, const void*, void*, int, int, int, int, long long, int, hipStream_t);
 void fn_reach_chunk(int*);
 int fn_reach_scan(const void*, void*, int, int, int, int, hipStream_t);
 int fn_reach_stats(const void*, const void*, const void*, const void*, void*, int, int, int, int, long long, int, int,
@@ -824,6 +827,38 @@ PYBIND11_MODULE(_C, m) {
         "edt_stats");
   }, py::arg("ids"), py::arg("offsets"), py::arg("d2"), py::arg("raw"), py::arg("N"), py::arg("D"), py::arg("H"),
      py::arg("W"), py::arg("T"), py::arg("st"), py::arg("ext"));
+  // walls between feature instances (nearest.hip): ids int32 [N][D][H][W] (a seed of label ids: ids > 0), D, H, W <=
+  // 128; t and nn int64 [N][2][D][H][W], which may be one buffer: per voxel the keys d2 << 32 | label of the nearest
+  // label and of the nearest other label ((1 << 30) << 32: none); passes bit 0 writes t (over the seeds of the
+  // voxel's plane), bit 1 nn from t; ext = {numel(ids), numel(t), numel(nn)}
+  m.def("nn_chunk", []() {
+    int t[2];
+    fn_nn_chunk(t);
+    return py::make_tuple(t[0], t[1]);
+  });
+  m.def("nn_transform", [](uintptr_t ids, uintptr_t t, uintptr_t nn, int N, int D, int H, int W, int passes,
+                           uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "nn_transform", "ids");
+    fits(ext, 1, prod({N, 2, D, H, W}), "nn_transform", "t");
+    fits(ext, 2, prod({N, 2, D, H, W}), "nn_transform", "nn");
+    chk(fn_nn_transform(P<const void*>(ids), P<void*>(t), P<void*>(nn), N, D, H, W, passes, S(st)), "nn_transform");
+  }, py::arg("ids"), py::arg("t"), py::arg("nn"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"),
+     py::arg("passes"), py::arg("st"), py::arg("ext"));
+  // ids int32 [N*V] and offsets int64 [N+1] as for access_stats, nn int64 [N][2][V] as nn_transform writes it; raw
+  // int64 [T][3] (fully rewritten): the smallest rank-1 d2 << 32 | index in the sample over the row's voxels (all
+  // ones: no voxel carries the row), its voxels with rank-1 d2 <= limit2, its voxels; 0 <= limit2 < 1 << 30; ext =
+  // {numel(ids), numel(offsets), numel(nn), numel(raw)}
+  m.def("wall_stats", [](uintptr_t ids, uintptr_t offsets, uintptr_t nn, uintptr_t raw, int N, int D, int H, int W,
+                         long long T, int limit2, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "wall_stats", "ids");
+    fits(ext, 1, N < 0 ? -1 : N + 1LL, "wall_stats", "offsets");
+    fits(ext, 2, prod({N, 2, D, H, W}), "wall_stats", "nn");
+    fits(ext, 3, prod({T, 3}), "wall_stats", "raw");
+    chk(fn_wall_stats(P<const void*>(ids), P<const void*>(offsets), P<const void*>(nn), P<void*>(raw), N, D, H, W, T,
+                      limit2, S(st)),
+        "wall_stats");
+  }, py::arg("ids"), py::arg("offsets"), py::arg("nn"), py::arg("raw"), py::arg("N"), py::arg("D"), py::arg("H"),
+     py::arg("W"), py::arg("T"), py::arg("limit2"), py::arg("st"), py::arg("ext"));
   // tool reach of feature instances (reach.hip): vol int32 [N][D][H][W], D, H, W <= 256; r6 int32 [N][6][D][H][W]
   // (written in full): the minimum of vol from each voxel to face k (+z -z +x -x +y -y) of the grid along that face's
   // axis, the voxel included; ext = {numel(vol), numel(r6)}

@@ -261,7 +261,7 @@ class FeatureNet3DSeg(nn.Module):
     @torch.no_grad()
     def instances(self, x: torch.Tensor, background: int | None = 0, connectivity: int = 6,
                   want_ids: bool = False, want_access: bool = False, want_dims: bool = False,
-                  want_reach: tuple | None = None, want_contacts: bool = False):
+                  want_reach: tuple | None = None, want_contacts: bool = False, want_walls: int | None = None):
         """The features in each sample: :meth:`predict`'s labels split into connected components
         -> ``(table, offsets, ids or None)`` on the model's device.  ``table`` int64 ``[T, 13]``
         has one row per component (``sample, class, voxels, root, z0, y0, x0, z1, y1, x1, sum_z,
@@ -291,22 +291,32 @@ class FeatureNet3DSeg(nn.Module):
         (after ``acc``, ``dim`` and ``reach``): row by row of ``table`` the voxel faces toward each
         side that meet material (``x != 0``), free space or the outside of the grid, and another
         component, and the voxels; and one row ``(row_a, row_b, face, faces)`` per pair of components
-        ``row_a < row_b`` and side of ``a`` on which they share faces (``ops.contact``)."""
-        from ..ops import access, ccl, contact, edt, reach
+        ``row_a < row_b`` and side of ``a`` on which they share faces (``ops.contact``).
+
+        With ``want_walls = limit2`` (None: off) ``wall`` int64 ``[T, 5]`` is appended after
+        everything else: row by row of ``table`` the smallest squared distance from one of the
+        component's voxels to a voxel of another component of the sample, the smallest index of a
+        voxel that attains it, the row of that other component (each ``-1`` where the sample has no
+        other), the component's voxels that have another component within the squared distance
+        ``limit2`` (``utils.seginstances.wall_threshold``), and all of them (``ops.nearest``).  It
+        needs no occupancy."""
+        from ..ops import access, ccl, contact, edt, nearest, reach
 
         if connectivity not in (6, 26):
             raise ValueError(f"instances: connectivity must be 6 or 26, not {connectivity!r}")
         labels = self.predict(x)
         roots, flags = ccl.connected_components(labels, background, connectivity, return_flags=True)
         more = want_access or want_dims or want_reach is not None or want_contacts
-        ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids or more, flags=flags)
-        if not more:
+        walls = want_walls is not None
+        ids, table, offsets = ccl.instance_table(labels, roots, want_ids=want_ids or more or walls, flags=flags)
+        if not more and not walls:
             return table, offsets, ids
-        occ = (x != 0).to(device=labels.device, dtype=torch.uint8)
-        if occ.dim() == 5:                       # [N, S, S, S, C]: material in any channel
-            occ = occ.amax(-1)
-        occ = occ.reshape(labels.shape)
         out = [table, offsets, ids if want_ids else None]
+        if more:
+            occ = (x != 0).to(device=labels.device, dtype=torch.uint8)
+            if occ.dim() == 5:                   # [N, S, S, S, C]: material in any channel
+                occ = occ.amax(-1)
+            occ = occ.reshape(labels.shape)
         if want_access:
             out.append(access.access_table(ids, offsets, occ, rows=table.shape[0])[0])
         d2 = None
@@ -318,6 +328,8 @@ class FeatureNet3DSeg(nn.Module):
             out.append(reach.reach_table(ids, offsets, occ, need2, cut2, rows=table.shape[0], d2=d2)[0])
         if want_contacts:
             out.extend(contact.contact_table(ids, offsets, occ, rows=table.shape[0]))
+        if walls:
+            out.append(nearest.wall_table(ids, offsets, want_walls, rows=table.shape[0])[0])
         return tuple(out)
 
     def match(self, x: torch.Tensor, y: torch.Tensor, background: int | None = 0, connectivity: int = 6):

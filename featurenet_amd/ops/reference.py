@@ -374,6 +374,115 @@ def dimension_table(ids: torch.Tensor, offsets: torch.Tensor, d2: torch.Tensor) 
     return dim
 
 
+NN_MAX_S = 128             # longest axis nearest_labels takes (the kernels' column strip of key pairs fills the LDS)
+NN_NONE = EDT_INF << 32    # the key of a missing rank
+WALL_NCOL = 5              # gap2 at other thin voxels
+_NN_CHUNK = 1 << 22        # voxels of the label volumes that nearest_labels holds at a time
+
+
+def nearest_labels(ids: torch.Tensor) -> torch.Tensor:
+    """Labelled distance transform of ``ids`` int32 ``[N, D, H, W]`` (a voxel is a seed of label
+    ``ids`` when ``ids > 0``) -> ``nn`` int64 ``[N, 2, D, H, W]`` of keys ``d2 << 32 | label``.  With
+    ``dist2_L(v)`` the smallest ``(z-z')^2 + (y-y')^2 + (x-x')^2`` over the seeds of label ``L`` in
+    ``v``'s sample, rank 0 of ``v`` is the smallest key ``dist2_L(v) << 32 | L`` over the sample's
+    labels -- the nearest label, among equally near ones the smallest -- and rank 1 the smallest key
+    over the other labels; a missing rank (no seed / fewer than two labels in the sample) is
+    ``NN_NONE = EDT_INF << 32``.  Each axis is at most ``NN_MAX_S``.
+
+    Label by label, straight from the definition: one :func:`distance_sq` per label present -- or,
+    for a label of fewer seeds than the transform has steps, the distances from every voxel to each
+    of its seeds (predicted labels break into thousands of such specks) -- then the smallest key and
+    the smallest key of another label over all of them, a chunk of labels or seeds at a time.  The
+    oracle of ``nn_xy`` / ``nn_z`` (which keep two keys through three separable passes instead) and
+    the CPU path of ``ops.nearest.nearest_labels``."""
+    if ids.dim() != 4 or ids.dtype != torch.int32:
+        raise ValueError(f"nearest_labels: ids must be int32 [N, D, H, W], not {ids.dtype} {tuple(ids.shape)}")
+    if max(ids.shape[1:]) > NN_MAX_S:
+        raise ValueError(f"nearest_labels: each of D, H, W is at most {NN_MAX_S}, not {tuple(ids.shape[1:])}")
+    N, D, H, W = ids.shape
+    V, dev = D * H * W, ids.device
+    nn = torch.full((N, 2, V), NN_NONE, dtype=torch.int64, device=dev)
+    if nn.numel() == 0:
+        return nn.view(N, 2, D, H, W)
+
+    def top2(best, keys):                        # the two best keys of distinct labels among best [2, V] and keys [K, V]
+        keys = torch.cat([best, keys])
+        a = keys.min(0).values
+        return torch.stack([a, torch.where((keys & 0xFFFFFFFF) == (a & 0xFFFFFFFF), NN_NONE, keys).min(0).values])
+
+    per = max(1, _NN_CHUNK // V)
+    lin = torch.arange(V, device=dev)
+    zyx = torch.stack([lin // (H * W), lin // W % H, lin % W])                # [3, V]
+    for n in range(N):
+        flat = ids[n].reshape(-1)
+        seeds = torch.nonzero(flat > 0).view(-1)
+        labels, which, counts = torch.unique(flat[seeds], return_inverse=True, return_counts=True)
+        few = counts < D + H + W
+        best = nn[n]
+        at = seeds[few[which]]                   # the seeds of the labels of few seeds: all pairs (voxel, seed)
+        for c in range(0, len(at), per):
+            s = at[c:c + per]
+            d2 = ((zyx[:, None, :] - zyx[:, s, None]) ** 2).sum(0)
+            best = top2(best, d2 << 32 | flat[s].to(torch.int64)[:, None])
+        many = labels[~few]
+        for c in range(0, len(many), per):
+            ls = many[c:c + per].view(-1, 1, 1, 1)
+            d2 = distance_sq((ids[n][None] == ls).to(torch.uint8)).to(torch.int64)
+            best = top2(best, (d2 << 32 | ls.to(torch.int64)).view(-1, V))
+        nn[n] = best
+    return nn.view(N, 2, D, H, W)
+
+
+def wall_decode(raw: torch.Tensor, offsets: torch.Tensor, nn: torch.Tensor) -> torch.Tensor:
+    """The wall table int64 ``[T, 5]`` from its raw form int64 ``[T, 3]`` (the smallest ``rank-1 d2 <<
+    32 | index in the sample`` over the row's voxels, the thin voxels, the voxels), over ``T`` rows:
+    the sample of a row is the one whose ``offsets`` hold it, and ``other`` is read from rank 1 of
+    ``nn`` at ``at``."""
+    T = raw.shape[0]
+    N, V = nn.shape[0], nn[0, 0].numel()
+    key, thin, vox = raw.unbind(1)
+    d = key >> 32
+    has = (vox > 0) & (d >= 0) & (d < EDT_INF)
+    at = torch.where(has, key & 0xFFFFFFFF, 0).clamp_(max=V - 1)       # (an index of a voxel, whatever raw holds)
+    n = (torch.bucketize(torch.arange(T, device=raw.device), offsets[1:].contiguous(), right=True)).clamp_(max=N - 1)
+    label = nn[:, 1].reshape(-1)[n * V + at] & 0xFFFFFFFF
+    minus = torch.full_like(key, -1)
+    return torch.stack([torch.where(has, d, minus), torch.where(has, at, minus),
+                        torch.where(has, offsets[:-1][n] + label - 1, minus), thin, vox], 1)
+
+
+def wall_table(ids: torch.Tensor, offsets: torch.Tensor, nn: torch.Tensor, limit2: int = 0) -> torch.Tensor:
+    """Wall table of an instance-id volume over its labelled transform -> int64 ``[T, 5]``.
+
+    ``ids`` int32 ``[N, D, H, W]`` and ``offsets`` int64 ``[N + 1]`` as :func:`instance_table` gives
+    them (``T = offsets[-1]``), ``nn`` int64 ``[N, 2, D, H, W]`` (:func:`nearest_labels` of ``ids``).
+    Row ``offsets[n] + id - 1`` holds, of id ``id`` of sample ``n``: ``gap2``, the smallest rank-1
+    distance over its voxels -- the squared distance between the centres of the nearest voxels of the
+    instance and of any other instance of the sample; ``at``, the smallest linear index ``(z * H +
+    y) * W + x`` within the sample of a voxel that attains it; ``other``, the table row ``offsets[n]
+    + id' - 1`` of rank 1's id at that voxel; ``thin``, its voxels whose rank-1 distance is ``<=
+    limit2``; ``voxels``, all of them.  ``gap2, at, other`` are ``-1`` where the sample has no other
+    instance or no voxel carries the row; a voxel with id 0 or whose row lies outside the table counts
+    nowhere.  Exact integers: the oracle of ``wall_stats`` and the CPU path of
+    ``ops.nearest.wall_table``."""
+    N, D, H, W = ids.shape
+    dev = ids.device
+    T = int(offsets[-1])
+    row = ids.to(torch.int64) + offsets.to(torch.int64)[:-1].view(N, 1, 1, 1) - 1
+    fg = (ids > 0) & (row >= 0) & (row < T)
+    raw = torch.zeros(T, 3, dtype=torch.int64, device=dev)
+    if T == 0 or ids.numel() == 0:
+        return torch.cat([torch.full((T, 3), -1, dtype=torch.int64, device=dev), raw[:, 1:]], 1)
+    rows, d = row[fg], (nn[:, 1] >> 32)[fg]
+    lin = torch.arange(D * H * W, device=dev).view(1, D, H, W).expand(ids.shape)[fg]
+    # the smallest d2 and, among equals, the smallest index: one min over (d2, index)
+    raw[:, 0] = torch.full((T,), -1, dtype=torch.int64, device=dev).scatter_reduce(
+        0, rows, d << 32 | lin, "amin", include_self=False)
+    raw[:, 1] = torch.bincount(rows[d <= limit2], minlength=T)
+    raw[:, 2] = torch.bincount(rows, minlength=T)
+    return wall_decode(raw, offsets.to(torch.int64), nn)
+
+
 REACH_NCOL = 15            # entry2 of the six faces, reached from each, from none, machinable, voxels
 
 

@@ -6,7 +6,8 @@ table (``ops.access.access_table``) also the voxels open toward each face of the
 largest squared distance from one of its voxels to the material, and where that voxel lies; with a
 reach table (``ops.reach.reach_table``) also what a given tool reaches from each face and clears; with
 the contact tables (``ops.contact.contact_table``) also the area of its walls, of its openings and of
-the faces it shares with other instances, side by side, and which instances those are.
+the faces it shares with other instances, side by side, and which instances those are; with a wall
+table (``ops.nearest.wall_table``) also how close it comes to another instance without touching it.
 """
 from __future__ import annotations
 
@@ -43,6 +44,26 @@ def tool_thresholds(t) -> tuple:
     return need2, cut2
 
 
+def wall_threshold(t) -> int:
+    """``limit2`` of a wall thickness of ``t`` voxels, in exact arithmetic: a wall of ``w`` whole
+    voxels between two features puts their nearest voxel centres ``w + 1`` apart, so the voxels that
+    have another feature behind a wall of at most ``t`` voxels are those whose squared distance to it
+    is at most ``limit2 = floor((t + 1)^2)``.  ``t`` is an int, a float (taken at its exact binary
+    value), a ``Fraction`` or a decimal string, ``>= 0``."""
+    if isinstance(t, bool):
+        raise ValueError(f"wall_threshold: the wall thickness must be a number, not {t!r}")
+    try:
+        w = Fraction(t)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"wall_threshold: the wall thickness must be a finite number, not {t!r}") from None
+    if w < 0:
+        raise ValueError(f"wall_threshold: the wall thickness must be >= 0, not {t!r}")
+    limit2 = math.floor((w + 1) ** 2)
+    if limit2 >= EDT_INF:
+        raise ValueError(f"wall_threshold: a wall of {t!r} voxels is thicker than any grid")
+    return limit2
+
+
 @dataclass
 class FeatureInstance:
     """One component of one class in one sample."""
@@ -65,6 +86,11 @@ class FeatureInstance:
     open_area: tuple | None = None      # per side, its voxel faces that meet free space or the outside of the grid
     shared_area: tuple | None = None    # per side, its voxel faces that meet another instance
     neighbors: tuple | None = None      # (id, face, faces): instance ``id`` of the sample lies toward ``face`` on ``faces`` faces
+    walls: bool = False            # the four below were computed (they are None where the part has no other instance)
+    gap2: int | None = None        # the smallest squared distance from a voxel's centre to another instance's voxel's
+    gap_at: tuple | None = None    # (z, y, x) of the first voxel, in raster order, that attains it
+    gap_to: int | None = None      # the id, in the sample's ``ids`` volume, of the instance nearest to that voxel
+    thin_voxels: int | None = None      # its voxels with another instance within the wall limit (None: no limit given)
 
     @property
     def clearance(self) -> float | None:
@@ -80,6 +106,19 @@ class FeatureInstance:
         material voxel: ``max(0, 2 * clearance - 1)``; None without dimensions."""
         c = self.clearance
         return None if c is None else max(0.0, 2.0 * c - 1.0)
+
+    @property
+    def gap(self) -> float | None:
+        """The distance from the centre of the voxel nearest to another instance to the centre of
+        that instance's nearest voxel, in voxels; None without walls or alone in the part."""
+        return None if self.gap2 is None else math.sqrt(self.gap2)
+
+    @property
+    def min_wall(self) -> float | None:
+        """The thinnest wall toward another instance, in voxels: ``max(0, gap - 1)`` (0: they share a
+        face, edge or corner); None without walls or alone in the part."""
+        g = self.gap
+        return None if g is None else max(0.0, g - 1.0)
 
     def entry_diameter(self, face: str) -> float | None:
         """The diameter in voxels of the largest ball that reaches at least one voxel of the feature
@@ -160,7 +199,8 @@ class FeatureInstance:
         reach also ``tool`` (need2, cut2), ``entry2`` and ``reachable`` (face -> value), ``tool_faces``
         (at ``min_fraction``), ``unreachable``, ``machinable`` and ``residual``; with contacts also
         ``wall_area``, ``open_area``, ``shared_area`` and ``floor`` (face -> faces), ``surface`` and
-        ``neighbors`` (a list of ``{"id", "face", "faces"}``)."""
+        ``neighbors`` (a list of ``{"id", "face", "faces"}``); with walls also ``gap2``, ``gap_at``,
+        ``gap_to``, ``min_wall`` (each None alone in the part) and ``thin_voxels``."""
         d = {"id": self.id, "class": self.cls, "voxels": self.voxels, "bbox": list(self.bbox),
              "centroid": list(self.centroid)}
         if self.access is not None:
@@ -179,11 +219,14 @@ class FeatureInstance:
                      shared_area=dict(zip(FACES, self.shared_area)), floor={f: self.floor(f) for f in FACES},
                      surface=self.surface,
                      neighbors=[{"id": i, "face": f, "faces": c} for i, f, c in self.neighbors])
+        if self.walls:
+            d.update(gap2=self.gap2, gap_at=None if self.gap_at is None else list(self.gap_at), gap_to=self.gap_to,
+                     min_wall=self.min_wall, thin_voxels=self.thin_voxels)
         return d
 
     @staticmethod
     def from_table(table, offsets, min_voxels: int = 1, access=None, dims=None, shape=None, reach=None,
-                   tool=None, contacts=None) -> "list[list[FeatureInstance]]":
+                   tool=None, contacts=None, walls=None, thin: bool = True) -> "list[list[FeatureInstance]]":
         """Per-sample record lists from an instance table int64 ``[T, 13]`` and its ``offsets``
         ``[N + 1]`` (tensors or arrays).  Components of fewer than ``min_voxels`` voxels are left
         out; the others keep their ``id``.  ``access``: the access table int64 ``[T, 8]`` of the
@@ -192,7 +235,9 @@ class FeatureInstance:
         ``reach``: the reach table int64 ``[T, 15]`` of the same rows, or None; with it ``tool``, the
         ``(need2, cut2)`` it was made for.  ``contacts``: ``(contact, adj)``, the contact table int64
         ``[T, 19]`` of the same rows and its pair list int64 ``[P, 4]``, or None; a neighbour that
-        ``min_voxels`` leaves out of the lists still appears in ``neighbors``, by its id."""
+        ``min_voxels`` leaves out of the lists still appears in ``neighbors``, by its id.  ``walls``:
+        the wall table int64 ``[T, 5]`` of the same rows, or None; it needs ``shape`` too, and with
+        ``thin=False`` (no limit was asked for) ``thin_voxels`` stays None."""
         tab = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.int64).reshape(-1, 13)
         off = np.asarray(offsets.cpu() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
         acc = None
@@ -230,6 +275,14 @@ class FeatureInstance:
             for a, b, k, faces in adj.tolist():      # a sees b toward k, b sees a toward the opposite side
                 near[a].append((b - int(first[b]) + 1, k, faces))
                 near[b].append((a - int(first[a]) + 1, k ^ 1, faces))
+        wal = None
+        if walls is not None:
+            wal = np.asarray(walls.cpu() if hasattr(walls, "cpu") else walls, dtype=np.int64).reshape(-1, 5)
+            if len(wal) != len(tab) or not np.array_equal(wal[:, 4], tab[:, 2]):
+                raise ValueError("from_table: the wall table does not belong to this instance table")
+            if shape is None or len(shape) != 3:
+                raise ValueError("from_table: walls needs shape = (D, H, W)")
+            _, H, W = (int(s) for s in shape)
         out = []
         for n in range(len(off) - 1):
             recs = []
@@ -255,6 +308,12 @@ class FeatureInstance:
                     rec.wall_area, rec.open_area = tuple(int(v) for v in con[k, :6]), tuple(int(v) for v in con[k, 6:12])
                     rec.shared_area = tuple(int(v) for v in con[k, 12:18])
                     rec.neighbors = tuple((i, FACES[f], c) for i, f, c in sorted(near[k]))
+                if wal is not None:
+                    gap2, at, other = (int(v) for v in wal[k, :3])
+                    rec.walls, rec.thin_voxels = True, int(wal[k, 3]) if thin else None
+                    if gap2 >= 0:
+                        rec.gap2, rec.gap_at = gap2, (at // (H * W), at // W % H, at % W)
+                        rec.gap_to = other - int(off[n]) + 1
                 recs.append(rec)
             out.append(recs)
         return out
