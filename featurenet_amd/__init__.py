@@ -10,7 +10,8 @@ __version__ = "0.1.0"
 # stays cheap and does not pull in torch-heavy modules until they are used.
 _API = ("train", "classify", "segment", "extract_features", "label_components", "evaluate", "evaluate_segmentation",
         "evaluate_features", "match_features", "generate_parts", "voxelize", "distance_transform", "EDT_INF", "load", "save",
-        "build_model", "search", "TrainResult", "tool_reach", "nearest_instances")
+        "build_model", "search", "TrainResult", "tool_reach", "nearest_instances", "isolate_features",
+        "recognize")
 
 
 def __getattr__(name):

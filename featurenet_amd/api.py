@@ -1,5 +1,5 @@
 """Public Python API: ``train()``, ``classify()``, ``segment()``, ``extract_features()``,
-``label_components()``, ``evaluate()``, ``evaluate_segmentation()``, ``evaluate_features()``,
+``label_components()``, ``recognize()``, ``isolate_features()``, ``evaluate()``, ``evaluate_segmentation()``, ``evaluate_features()``,
 ``match_features()``, ``generate_parts()``, ``voxelize()``, ``distance_transform()``, ``load()``, ``save()``, ``build_model()`` and ``search()``.
 
 Reference parity: the de-facto entry point of the reference is the
@@ -282,7 +282,7 @@ def evaluate_segmentation(model, x, y, batch_size: int = 32, device=None, packed
 def extract_features(model, x, batch_size: int = 32, device=None, packed_size: int | None = None,
                      background: int | None = 0, connectivity: int = 6, min_voxels: int = 1,
                      return_ids: bool = False, access: bool = False, dimensions: bool = False, tool=None,
-                     contacts: bool = False, walls=False):
+                     contacts: bool = False, walls=False, classifier=None):
     """The machining features of each part -> (one list of :class:`FeatureInstance` per sample,
     ids int32 [N, S, S, S] or None).
 
@@ -333,6 +333,13 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
     that have another feature behind a wall of at most ``t`` voxels.  The labelled distance
     transform runs on the model's device (``ops.nearest``); 5 more integers per component cross to
     the host.
+
+    With ``classifier`` -- a :class:`FeatureNet3D` or a checkpoint path of one, with the grid's size as
+    its input size -- every record also carries the single-feature classifier's second opinion:
+    ``recognized`` is the class (0..C-1) it gives to the component put alone into a solid stock block
+    (``ops.isolate``, the FeatureNet paper's recipe), ``recognized_prob`` that class's probability, and
+    ``agrees`` says whether ``cls == recognized + 1``.  The parts are made and classified on the model's
+    device; two numbers per component cross to the host.
     """
     from .utils.seginstances import FeatureInstance, tool_thresholds
 
@@ -340,6 +347,8 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
     limit2 = _wall_limit(walls)
     if isinstance(model, (str, Path)):
         model, _ = load(model, device)
+    if classifier is not None:
+        classifier, _ = _classifier(classifier, next(model.parameters()).device, "extract_features()")
     if not isinstance(model, FeatureNet3DSeg):
         raise ValueError(f"extract_features() takes a FeatureNet3DSeg model, not {type(model).__name__} "
                          "(see classify())")
@@ -357,7 +366,8 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
             xb = unpack_voxels(xb, packed_size)
         xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
         table, offsets, idb, *more = model.instances(xb, background=background, connectivity=connectivity,
-                                                     want_ids=return_ids, want_access=access, want_dims=dimensions,
+                                                     want_ids=return_ids or classifier is not None,
+                                                     want_access=access, want_dims=dimensions,
                                                      want_reach=thresholds, want_contacts=contacts,
                                                      want_walls=limit2)
         wall = None
@@ -367,11 +377,17 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
         if contacts:
             *more, con, adj = more
             pairs = (con, adj)
+        seen = None
+        if classifier is not None:
+            from .ops import isolate
+
+            seen = isolate.recognize_table(classifier, idb, table, offsets, rows=table.shape[0],
+                                           min_voxels=min_voxels)[:2]
         feats += FeatureInstance.from_table(table, offsets, min_voxels, access=more[0] if access else None,
                                             dims=more[1 if access else 0] if dimensions else None,
                                             shape=tuple(xb.shape[1:4]),
                                             reach=more[-1] if thresholds is not None else None, tool=thresholds,
-                                            contacts=pairs, walls=wall, thin=walls is not True)
+                                            contacts=pairs, walls=wall, thin=walls is not True, recognized=seen)
         if return_ids:
             ids.append(idb.cpu())
     if not return_ids:
@@ -382,7 +398,8 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
 
 @torch.no_grad()
 def label_components(labels, background: int | None = 0, connectivity: int = 6, device=None, occupancy=None,
-                     dimensions: bool = False, tool=None, contacts: bool = False, walls=False):
+                     dimensions: bool = False, tool=None, contacts: bool = False, walls=False, classifier=None,
+                     min_voxels: int = 1, batch_size: int = 256):
     """Connected components of label volumes the caller already has (ground truth, say) ->
     (ids int32 [N, D, H, W], one list of :class:`FeatureInstance` per sample).
 
@@ -395,9 +412,13 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     diameter in voxels, which needs ``occupancy`` too) the reach of that tool as its ``tool`` does,
     ``contacts`` (which needs ``occupancy`` too) the wall, open and shared areas and the neighbours
     as its ``contacts`` does, ``walls`` (True or a wall thickness in voxels; it needs no
-    ``occupancy``) the gap to the nearest other feature as its ``walls`` does.
+    ``occupancy``) the gap to the nearest other feature as its ``walls`` does, ``classifier`` (a
+    :class:`FeatureNet3D` or a checkpoint path of one; it needs no ``occupancy``) the single-feature
+    classifier's ``recognized`` / ``recognized_prob`` as its ``classifier`` does: the grid is resampled
+    to the classifier's input size, ``batch_size`` parts run at a time, and components of fewer than
+    ``min_voxels`` voxels are not classified -- they stay in the lists with ``recognized = None``.
     """
-    from .ops import access, ccl, contact, edt, nearest, reach
+    from .ops import ccl
     from .utils.seginstances import FeatureInstance, tool_thresholds
 
     if dimensions and occupancy is None:
@@ -420,6 +441,8 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
         raise ValueError(f"label_components(): labels must be [N, D, H, W], not {tuple(lt.shape)}")
     if lt.dtype != torch.uint8 and lt.numel() and (int(lt.min()) < 0 or int(lt.max()) > 255):
         raise ValueError("label_components(): label values must lie in 0..255")
+    if classifier is not None:
+        classifier, device = _classifier(classifier, device, "label_components()")
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
     ot = None
@@ -432,21 +455,193 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     lt = lt.to(device).to(torch.uint8).contiguous()
     roots, flags = ccl.connected_components(lt, background, connectivity, return_flags=True)
     ids, table, offsets = ccl.instance_table(lt, roots, want_ids=True, flags=flags)
+    occ = None if ot is None else (ot.to(device) != 0).to(torch.uint8)
+    more = _geometry_tables(ids, table, offsets, occ, occ is not None, dimensions, thresholds, contacts, limit2)
+    seen = None
+    if classifier is not None:
+        from .ops import isolate
+
+        seen = isolate.recognize_table(classifier, ids, table, offsets, rows=table.shape[0], min_voxels=min_voxels,
+                                       batch_size=batch_size)[:2]
+    return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets, shape=tuple(lt.shape[1:]), tool=thresholds,
+                                                         thin=walls is not True, recognized=seen, **more)
+
+
+def _geometry_tables(ids, table, offsets, occ, access: bool, dimensions: bool, thresholds, contacts: bool, limit2):
+    """The optional tables of an id volume as keyword arguments of ``FeatureInstance.from_table``
+    (``access``, ``dims``, ``reach``, ``contacts``, ``walls``), each None where it is not asked for.
+    Everything but ``walls`` needs the occupancy ``occ``."""
+    from .ops import access as access_, contact, edt, nearest, reach
+
     acc = dim = rch = d2 = pairs = wall = None
-    if ot is not None:
-        occ = (ot.to(device) != 0).to(torch.uint8)
-        acc, _ = access.access_table(ids, offsets, occ, rows=table.shape[0])
-        if dimensions:
-            dim, d2 = edt.dimension_table(ids, offsets, occ, rows=table.shape[0], want_d2=thresholds is not None)
-        if thresholds is not None:
-            rch, _ = reach.reach_table(ids, offsets, occ, *thresholds, rows=table.shape[0], d2=d2)
-        if contacts:
-            pairs = contact.contact_table(ids, offsets, occ, rows=table.shape[0])
+    T = table.shape[0]
+    if access:
+        acc, _ = access_.access_table(ids, offsets, occ, rows=T)
+    if dimensions:
+        dim, d2 = edt.dimension_table(ids, offsets, occ, rows=T, want_d2=thresholds is not None)
+    if thresholds is not None:
+        rch, _ = reach.reach_table(ids, offsets, occ, *thresholds, rows=T, d2=d2)
+    if contacts:
+        pairs = contact.contact_table(ids, offsets, occ, rows=T)
     if limit2 is not None:
-        wall, _ = nearest.wall_table(ids, offsets, limit2, rows=table.shape[0])
-    return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets, access=acc, dims=dim,
-                                                         shape=tuple(lt.shape[1:]), reach=rch, tool=thresholds,
-                                                         contacts=pairs, walls=wall, thin=walls is not True)
+        wall, _ = nearest.wall_table(ids, offsets, limit2, rows=T)
+    return {"access": acc, "dims": dim, "reach": rch, "contacts": pairs, "walls": wall}
+
+
+def _classifier(classifier, device, what: str):
+    """The ``classifier`` option -> ``(a FeatureNet3D on the device, that device)``: a checkpoint path is
+    loaded, ``device=None`` is where a module already lives."""
+    if isinstance(classifier, (str, Path)):
+        classifier, _ = load(classifier, device)
+    if not isinstance(classifier, FeatureNet3D):
+        raise ValueError(f"{what}: the classifier must be a FeatureNet3D, not {type(classifier).__name__} (a "
+                         "segmentation model labels voxels: pass it as the model)")
+    dev = next(classifier.parameters()).device if device is None else torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return classifier.to(dev), dev
+
+
+def _cut_stock(occ: torch.Tensor, stock: str, what: str):
+    """``window`` (None: the grid) of the ``stock`` option for an occupancy volume on its device."""
+    from .ops import isolate
+
+    if stock == "grid":
+        return None
+    if stock == "bbox":
+        return isolate.material_window(occ)
+    raise ValueError(f"{what}: stock must be 'grid' or 'bbox', not {stock!r}")
+
+
+@torch.no_grad()
+def isolate_features(ids, features=None, size: int | None = None, occupancy=None, stock: str = "grid",
+                     packed: bool = False, min_voxels: int = 1, device=None):
+    """Each feature of an ``ids`` volume alone in a solid stock block -> ``(parts, index)``: ``parts``
+    uint8 ``[M, S, S, S]`` (1 = material; the input of :func:`classify`), or with ``packed`` its bits,
+    uint8 ``[M, S^3 / 8]`` (``packed_size=S``), and ``index`` int64 ``[M, 2]``, the ``(sample, id)`` of
+    every part.
+
+    ``ids`` is ``[N, D, H, W]`` of an integer dtype, as :func:`extract_features` (``return_ids``),
+    :func:`label_components` and :func:`recognize` give it: a voxel ``> 0`` belongs to the feature of
+    that number in its sample.  ``features``: one list of :class:`FeatureInstance` per sample, the
+    features to cut out (their ``id`` and ``bbox`` are used); None: every id that occurs.  Features
+    of fewer than ``min_voxels`` voxels are left out.  The stock block is the whole grid
+    (``stock="grid"``) or the bounding box of the material of ``occupancy`` (``"bbox"``; non-zero:
+    material), scaled by its longest side to ``size`` voxels with the shorter sides centred; a
+    voxel looks at the source voxel under its centre, so a feature thinner than ``longest side /
+    size`` voxels can vanish.  ``size=None`` takes the grid's own size, which must then be a cube.
+    What lies outside the stock is free space (0); inside it everything but the feature itself is
+    material, other features too.  ``device`` defaults to the GPU when there is one (the
+    ``isolate_parts`` kernel), else the CPU reference path; the result is the same.
+    """
+    from .ops import isolate
+
+    it = torch.as_tensor(np.asarray(ids)) if not isinstance(ids, torch.Tensor) else ids
+    if it.is_floating_point() or it.is_complex() or it.dtype == torch.bool:
+        raise ValueError(f"isolate_features(): ids must be integers, not {it.dtype}")
+    if it.dim() != 4:
+        raise ValueError(f"isolate_features(): ids must be [N, D, H, W], not {tuple(it.shape)}")
+    N, D, H, W = it.shape
+    if size is None:
+        if not D == H == W:
+            raise ValueError(f"isolate_features(): size=None takes the grid's size, but {(D, H, W)} is no cube")
+        size = D
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 8 or size > 256 or size % 8:
+        raise ValueError(f"isolate_features(): size must be a multiple of 8 in [8, 256], not {size!r}")
+    if stock not in ("grid", "bbox"):
+        raise ValueError(f"isolate_features(): stock must be 'grid' or 'bbox', not {stock!r}")
+    if stock == "bbox" and occupancy is None:
+        raise ValueError("isolate_features(): stock='bbox' needs occupancy (the material whose box is the stock)")
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    it = it.to(device).to(torch.int32).contiguous()
+    window = None
+    if stock == "bbox":
+        ot = torch.as_tensor(np.asarray(occupancy)) if not isinstance(occupancy, torch.Tensor) else occupancy
+        if ot.shape != it.shape:
+            raise ValueError(f"isolate_features(): occupancy is {tuple(ot.shape)} but ids {tuple(it.shape)}")
+        window = isolate.material_window(ot.to(device))
+    if features is None:
+        top = int(it.max()) if it.numel() else 0
+        flat = it.clamp(min=0).reshape(N, -1).to(torch.int64) + (top + 1) * torch.arange(N, device=it.device)[:, None]
+        counts = torch.bincount(flat.reshape(-1), minlength=N * (top + 1)).view(N, top + 1)
+        counts[:, 0] = 0
+        index = torch.nonzero(counts >= max(1, int(min_voxels)))
+        box = torch.tensor([0, 0, 0, D - 1, H - 1, W - 1], dtype=torch.int64, device=it.device).expand(len(index), 6)
+    else:
+        if len(features) != N:
+            raise ValueError(f"isolate_features(): {N} samples but {len(features)} feature lists")
+        rows = [(n, f.id, *f.bbox) for n, fs in enumerate(features) for f in fs if f.voxels >= min_voxels]
+        both = torch.tensor(rows, dtype=torch.int64, device=it.device).reshape(-1, 8)
+        index, box = both[:, :2], both[:, 2:]
+    win = torch.tensor([0, 0, 0, D, H, W], dtype=torch.int64, device=it.device).expand(len(index), 6) \
+        if window is None else window[index[:, 0]]
+    sel = torch.cat([index, box, win], 1).to(torch.int32)
+    parts = isolate.isolate_instances(it, sel, int(size), 0 if packed else 1)
+    return parts.cpu().numpy(), index.cpu().numpy()
+
+
+@torch.no_grad()
+def recognize(classifier, voxels, stock: str = "grid", connectivity: int = 6, min_voxels: int = 1,
+              return_ids: bool = False, return_labels: bool = False, batch_size: int = 256, device=None,
+              access: bool = False, dimensions: bool = False, tool=None, contacts: bool = False, walls=False):
+    """The features of each part by the single-feature classifier alone, the multi-feature recipe of
+    the FeatureNet paper -> ``(features, ids or None, labels or None)``: one list of
+    :class:`FeatureInstance` per sample, ids int32 ``[N, D, H, W]`` with ``return_ids`` and labels
+    uint8 ``[N, D, H, W]`` with ``return_labels``.
+
+    ``classifier`` is a :class:`FeatureNet3D` or a checkpoint path of one; ``voxels`` is ``[N, D, H,
+    W]`` occupancy of an integer or bool dtype (non-zero: material), every axis at most 256.  The
+    removed volume -- ``voxels == 0`` inside the stock, which is the grid (``stock="grid"``) or the
+    bounding box of the material (``"bbox"``) -- is split into ``connectivity``-connected components
+    (``ops.ccl``), each component is put back alone into a solid stock block at the classifier's input
+    size and classified (``ops.isolate``), all on ``device`` (default: the GPU when there is one).
+    A record has ``recognized`` and ``recognized_prob``, and ``cls = 1 + recognized``, the label rule
+    of :func:`generate_parts`, so the records compare with those of a segmentation model; ``labels``
+    holds that ``cls`` on every voxel of the component and 0 elsewhere, ready for
+    :func:`match_features`.  Components of fewer than ``min_voxels`` voxels are left out of the lists
+    and of ``labels``; ``ids`` keeps them.  Features that touch are one component here: without a
+    segmentation model nothing tells them apart.  ``access``, ``dimensions``, ``tool``, ``contacts``
+    and ``walls`` as for :func:`extract_features`.
+    """
+    from .ops import ccl, isolate
+    from .utils.seginstances import FeatureInstance, tool_thresholds
+
+    thresholds = None if tool is None else tool_thresholds(tool)
+    limit2 = _wall_limit(walls)
+    if connectivity not in (6, 26):
+        raise ValueError(f"recognize(): connectivity must be 6 or 26, not {connectivity!r}")
+    vt = torch.as_tensor(np.asarray(voxels)) if not isinstance(voxels, torch.Tensor) else voxels
+    if vt.is_floating_point() or vt.is_complex():
+        raise ValueError(f"recognize(): voxels must be integers or bools, not {vt.dtype}")
+    if vt.dim() != 4:
+        raise ValueError(f"recognize(): voxels must be [N, D, H, W], not {tuple(vt.shape)}")
+    classifier, device = _classifier(classifier, device, "recognize()")
+    occ = (vt.to(device) != 0).to(torch.uint8).contiguous()
+    window = _cut_stock(occ, stock, "recognize()")
+    removed = occ == 0
+    if window is not None:
+        for axis in (1, 2, 3):
+            idx = torch.arange(occ.shape[axis], device=occ.device).view([-1 if a == axis else 1 for a in range(4)])
+            lo = window[:, axis - 1].view(-1, 1, 1, 1)
+            removed = removed & (idx >= lo) & (idx < lo + window[:, axis + 2].view(-1, 1, 1, 1))
+    removed = removed.to(torch.uint8)
+    roots, flags = ccl.connected_components(removed, 0, connectivity, return_flags=True)
+    ids, table, offsets = ccl.instance_table(removed, roots, want_ids=True, flags=flags)
+    T = table.shape[0]
+    cls, prob, _ = isolate.recognize_table(classifier, ids, table, offsets, rows=T, min_voxels=min_voxels,
+                                           window=window, batch_size=batch_size)
+    table = table.clone()
+    table[:, 1] = cls + 1
+    more = _geometry_tables(ids, table, offsets, occ, access, dimensions, thresholds, contacts, limit2)
+    feats = FeatureInstance.from_table(table, offsets, min_voxels, shape=tuple(occ.shape[1:]), tool=thresholds,
+                                       thin=walls is not True, recognized=(cls, prob), **more)
+    labels = None
+    if return_labels:
+        lut = torch.cat([table.new_zeros(1), table[:, 1]])                      # 0: no component
+        row = torch.where(ids > 0, ids.to(torch.int64) + offsets[:-1].view(-1, 1, 1, 1), 0)
+        labels = lut[row].to(torch.uint8).cpu().numpy()
+    return feats, (ids.cpu().numpy() if return_ids else None), labels
 
 
 def _wall_limit(walls):

@@ -16,6 +16,7 @@ classify   load a checkpoint and predict (npy / binvox folder)
 segment    per-voxel labels of a segmentation checkpoint -> .npy
 score      confusion matrix / per-class IoU / mIoU of a segmentation checkpoint against true labels
 features   the feature instances (connected components of the labels) of a segmentation checkpoint -> JSON
+recognize  the features of multi-feature parts by a single-feature classifier checkpoint alone -> JSON
 score-features
            predicted features matched to the true ones: per-class TP / FP / FN, F1 and panoptic quality
 generate-parts
@@ -247,10 +248,33 @@ def cmd_features(a) -> int:
                                       background=None if a.background < 0 else a.background,
                                       connectivity=a.connectivity, min_voxels=a.min_voxels, return_ids=bool(a.ids),
                                       access=a.access, dimensions=a.dimensions, tool=a.tool,
-                                      contacts=a.contacts, walls=False if a.walls is None else a.walls)
+                                      contacts=a.contacts, walls=False if a.walls is None else a.walls,
+                                      classifier=a.classifier or None)
     if a.ids:
         np.save(a.ids, ids)
     summary = json.dumps({"samples": [[f.to_dict(a.access_fraction) for f in fs] for fs in feats]})
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(summary + "\n")
+    print(summary)
+    return 0
+
+
+def cmd_recognize(a) -> int:
+    import numpy as np
+
+    from . import api
+
+    x = np.load(a.input, allow_pickle=False)
+    feats, ids, labels = api.recognize(a.model, x, stock=a.stock, connectivity=a.connectivity,
+                                       min_voxels=a.min_voxels, return_ids=bool(a.ids), return_labels=bool(a.labels),
+                                       device=a.device or None, access=a.access, dimensions=a.dimensions, tool=a.tool,
+                                       contacts=a.contacts, walls=False if a.walls is None else a.walls)
+    if a.ids:
+        np.save(a.ids, ids)
+    if a.labels:
+        np.save(a.labels, labels)
+    summary = json.dumps({"samples": [[f.to_dict() for f in fs] for fs in feats]})
     if a.json:
         with open(a.json, "w") as f:
             f.write(summary + "\n")
@@ -580,7 +604,31 @@ def build_parser() -> argparse.ArgumentParser:
     ft.add_argument("--walls", type=float, nargs="?", const=True, default=None, metavar="T",
                     help="add the gap to the nearest other feature of the part: gap2, gap_at, gap_to, min_wall; with T "
                          "also thin_voxels, the voxels with another feature behind a wall of at most T voxels")
+    ft.add_argument("--classifier", default="", metavar="CLF.fnk",
+                    help="add the single-feature classifier's opinion on every feature put alone into a solid stock "
+                         "block: recognized, recognized_prob, agrees")
     ft.set_defaults(fn=cmd_features)
+
+    rg = sub.add_parser("recognize", help="the features of multi-feature parts by a single-feature classifier "
+                                          "checkpoint alone: removed volume -> components -> each one alone in a "
+                                          "solid block -> class")
+    rg.add_argument("model", help="FeatureNet-3D classifier checkpoint (.fnk)")
+    rg.add_argument("input", help="[N, D, H, W] occupancy (.npy), non-zero = material")
+    rg.add_argument("--json", default="", metavar="OUT", help="also write the JSON document to this file")
+    rg.add_argument("--labels", default="", metavar="LABELS.npy",
+                    help="also write the label volume (uint8 .npy): 1 + class on every voxel of a feature, else 0")
+    rg.add_argument("--ids", default="", metavar="IDS.npy", help="also write the instance-id volume (int32 .npy)")
+    rg.add_argument("--stock", default="grid", choices=("grid", "bbox"),
+                    help="the stock the part was cut from: the whole grid, or the bounding box of the material")
+    rg.add_argument("--connectivity", type=int, default=6, choices=(6, 26))
+    rg.add_argument("--min-voxels", type=int, default=1, metavar="K", help="leave out smaller components")
+    rg.add_argument("--device", default="", help="cuda / cpu (default: where the checkpoint loads)")
+    rg.add_argument("--access", action="store_true", help="as for features")
+    rg.add_argument("--dimensions", action="store_true", help="as for features")
+    rg.add_argument("--tool", type=float, default=None, metavar="T", help="as for features")
+    rg.add_argument("--contacts", action="store_true", help="as for features")
+    rg.add_argument("--walls", type=float, nargs="?", const=True, default=None, metavar="T", help="as for features")
+    rg.set_defaults(fn=cmd_recognize)
 
     nr = sub.add_parser("nearest", help="labelled distance transform: the nearest and the nearest other instance of "
                                         "every voxel with their squared distances -> .npz (d2, nearest)")

@@ -66,6 +66,7 @@ void fn_reach_chunk(int*);
 int fn_reach_scan(const void*, void*, int, int, int, int, hipStream_t);
 int fn_reach_stats(const void*, const void*, const void*, const void*, void*, int, int, int, int, long long, int, int,
                    hipStream_t);
+int fn_isolate_parts(const void*, const void*, void*, int, int, int, int, long long, int, int, hipStream_t);
 void fn_contact_chunk(int*);
 int fn_contact_stats(const void*, const void*, const void*, void*, void*, void*, void*, int, int, int, int, long long,
                      long long, long long, hipStream_t);
@@ -918,6 +919,21 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("ids"), py::arg("occ"), py::arg("offsets"), py::arg("contact"), py::arg("keys"), py::arg("counts"),
      py::arg("lost"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("T"), py::arg("cap"),
      py::arg("probe"), py::arg("st"), py::arg("ext"));
+  // each selected instance alone in a solid stock block (isolate.hip): ids int32 [N][D][H][W], D, H, W <= 256 and
+  // N*D*H*W < 2^31; sel int32 [M][14] = n id | box z0 y0 x0 z1 y1 x1 | window z0 y0 x0 Lz Ly Lx (a row whose sample
+  // or window lies outside the grid gives a part of zeros); out on a 16-byte boundary: fmt 0 the bits, uint8
+  // [M][S^3/8], fmt 1 uint8 [M][S^3], fmt 2 bf16 [M][S^3]; S % 8 == 0, 8 <= S <= 256, M * S^3 < 2^31; ext =
+  // {numel(ids), numel(sel), numel(out)}
+  m.def("isolate_parts", [](uintptr_t ids, uintptr_t sel, uintptr_t out, int N, int D, int H, int W, long long M,
+                            int size, int fmt, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "isolate_parts", "ids");
+    fits(ext, 1, prod({M, 14}), "isolate_parts", "sel");
+    fits(ext, 2, size < 8 || size % 8 ? -1 : prod({M, size, size, size}) / (fmt == 0 ? 8 : 1), "isolate_parts",
+         "out");
+    chk(fn_isolate_parts(P<const void*>(ids), P<const void*>(sel), P<void*>(out), N, D, H, W, M, size, fmt, S(st)),
+        "isolate_parts");
+  }, py::arg("ids"), py::arg("sel"), py::arg("out"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"),
+     py::arg("M"), py::arg("size"), py::arg("fmt"), py::arg("st"), py::arg("ext"));
   // multi-feature parts from their parameter tables (partgen.hip): params int32 [N][K][16]; occ / labels / slots
   // uint8 [N][S][S][S] (8-byte aligned) and packed uint8 [N][S^3/8], each 0 = not wanted; S % 8 == 0, 8 <= S <=
   // 256, K <= 32; ext = {numel(params), numel(occ), numel(packed), numel(labels), numel(slots)}

@@ -782,3 +782,96 @@ def voxelize_tris(tris: torch.Tensor, offsets: torch.Tensor, size: int):
         occ[n] = odd[..., :S].to(torch.uint8)
         leaks[n] = odd[..., S].sum()
     return occ, leaks
+
+
+ISOLATE_NCOL = 14          # n id | box z0 y0 x0 z1 y1 x1 | window z0 y0 x0 Lz Ly Lx
+ISOLATE_MAX_S = 256        # longest grid axis and largest output size isolate_instances takes
+_ISOLATE_CHUNK = 1 << 24   # output voxels that isolate_instances gathers at a time
+
+
+def isolate_check(ids: torch.Tensor, sel: torch.Tensor, size, fmt) -> int:
+    """The argument checks of ``isolate_instances`` that need no value of ``sel`` -> ``S``."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 4:
+        got = f"{ids.dtype} {tuple(ids.shape)}" if isinstance(ids, torch.Tensor) else type(ids).__name__
+        raise ValueError(f"isolate_instances: ids must be an int32 [N, D, H, W] tensor, not {got}")
+    if not isinstance(sel, torch.Tensor) or sel.dtype != torch.int32 or sel.dim() != 2 \
+            or sel.shape[1] != ISOLATE_NCOL:
+        got = f"{sel.dtype} {tuple(sel.shape)}" if isinstance(sel, torch.Tensor) else type(sel).__name__
+        raise ValueError(f"isolate_instances: sel must be an int32 [M, {ISOLATE_NCOL}] tensor, not {got}")
+    if sel.device != ids.device:
+        raise ValueError(f"isolate_instances: ids ({ids.device}) and sel ({sel.device}) must be on one device")
+    if isinstance(size, bool) or not isinstance(size, int) or size < 8 or size > ISOLATE_MAX_S or size % 8:
+        raise ValueError(f"isolate_instances: size must be a multiple of 8 in [8, {ISOLATE_MAX_S}], not {size!r}")
+    if fmt not in (0, 1, 2):
+        raise ValueError(f"isolate_instances: fmt must be 0 (packed bits), 1 (uint8) or 2 (bf16), not {fmt!r}")
+    if max(ids.shape[1:]) > ISOLATE_MAX_S:
+        raise ValueError(f"isolate_instances: every grid axis must be at most {ISOLATE_MAX_S}, not "
+                         f"{tuple(ids.shape[1:])}")
+    if ids.numel() >= 1 << 31:
+        raise ValueError("isolate_instances: a batch must have fewer than 2^31 voxels; split it by samples")
+    return int(size)
+
+
+def isolate_bad_rows(sel: torch.Tensor, shape) -> torch.Tensor:
+    """bool ``[M]``: the rows of ``sel`` whose sample or window does not lie in a grid of ``shape = (N, D, H,
+    W)``, on the device of ``sel``."""
+    N = int(shape[0])
+    dims = torch.tensor([int(s) for s in shape[1:]], dtype=torch.int64, device=sel.device)
+    s = sel.to(torch.int64)
+    w0, L = s[:, 8:11], s[:, 11:14]
+    return (s[:, 0] < 0) | (s[:, 0] >= N) | ((L < 1) | (w0 < 0) | (w0 + L > dims)).any(1)
+
+
+def isolate_instances(ids: torch.Tensor, sel: torch.Tensor, size: int, fmt: int = 1) -> torch.Tensor:
+    """Each selected instance alone in a solid stock block, at the classifier's resolution.
+
+    ``ids`` int32 ``[N, D, H, W]`` (``instance_table``'s), ``sel`` int32 ``[M, 14]``, a row being ``n, id``
+    (the sample and the instance's number in it), ``bz0, by0, bx0, bz1, by1, bx1`` (an inclusive box in the
+    source grid) and ``wz0, wy0, wx0, Lz, Ly, Lx`` (the source window that becomes the stock block: ``L >=
+    1``, inside the grid).  Output voxel ``o`` of an axis of part ``m`` looks, with ``Lmax = max(Lz, Ly, Lx)``
+    and ``L``, ``w0`` those of the axis, at the window's voxel
+
+        ``s = floor_div((2 o + 1) Lmax - (Lmax - L) S, 2 S)``
+
+    -- the centre of ``o`` under the one scale ``Lmax / S``, the shorter axes centred, a centre on a source
+    boundary going to the higher index.  A voxel with ``s < 0`` or ``s >= L`` on any axis lies outside the
+    stock and is 0 (free space); otherwise its source voxel is ``v = w0 + s``, and it is 0 (the feature) iff
+    ``v`` lies in the box and ``ids[n, v] == id``, else 1 (material, also where the source holds another
+    instance).  With ``L == Lmax == S`` and ``w0 == 0`` the part is ``ids[n] != id`` inside the box.
+
+    ``fmt`` 0: bits, uint8 ``[M, S^3 / 8]``, bit ``i & 7`` of byte ``i >> 3`` for ``i = (Z S + Y) S + X``; 1:
+    uint8 ``[M, S, S, S]``; 2: bfloat16 ``[M, S, S, S, 1]``.  Exact integers: the oracle of ``isolate_parts``
+    and the CPU path of ``ops.isolate``."""
+    S = isolate_check(ids, sel, size, fmt)
+    N, D, H, W = ids.shape
+    M, dev = sel.shape[0], ids.device
+    if M and bool(isolate_bad_rows(sel, ids.shape).any()):
+        raise ValueError(f"isolate_instances: a row of sel names a sample or a window outside the grid "
+                         f"{tuple(ids.shape)}")
+    out = torch.empty(M, S, S, S, dtype=torch.uint8, device=dev)
+    s64 = sel.to(torch.int64)
+    o = torch.arange(S, dtype=torch.int64, device=dev)
+    step = max(1, _ISOLATE_CHUNK // S ** 3)
+    for lo in range(0, M, step):
+        r = s64[lo:lo + step]
+        L, w0 = r[:, 11:14], r[:, 8:11]
+        Lmax = L.amax(1, keepdim=True)
+        num = (2 * o + 1) * Lmax[:, :, None] - ((Lmax - L) * S)[:, :, None]          # [m, 3, S]
+        s = torch.div(num, 2 * S, rounding_mode="floor")
+        inside = (s >= 0) & (s < L[:, :, None])
+        v = w0[:, :, None] + s
+        inbox = (v >= r[:, 2:5, None]) & (v <= r[:, 5:8, None])
+        dims = torch.tensor([D, H, W], dtype=torch.int64, device=dev).view(1, 3, 1)
+        vc = torch.minimum(v.clamp(min=0), dims - 1)
+        got = ids[r[:, 0].view(-1, 1, 1, 1), vc[:, 0, :, None, None], vc[:, 1, None, :, None],
+                  vc[:, 2, None, None, :]]
+        cube = lambda t: t[:, 0, :, None, None] & t[:, 1, None, :, None] & t[:, 2, None, None, :]   # noqa: E731
+        stock = cube(inside)
+        feature = stock & cube(inbox) & (got == r[:, 1].view(-1, 1, 1, 1))
+        out[lo:lo + step] = (stock & ~feature).to(torch.uint8)
+    if fmt == 1:
+        return out
+    if fmt == 2:
+        return out.to(torch.bfloat16).unsqueeze(-1)
+    weights = 1 << torch.arange(8, dtype=torch.int32, device=dev)
+    return (out.reshape(M, S ** 3 // 8, 8).to(torch.int32) * weights).sum(-1).to(torch.uint8)

@@ -91,6 +91,14 @@ class FeatureInstance:
     gap_at: tuple | None = None    # (z, y, x) of the first voxel, in raster order, that attains it
     gap_to: int | None = None      # the id, in the sample's ``ids`` volume, of the instance nearest to that voxel
     thin_voxels: int | None = None      # its voxels with another instance within the wall limit (None: no limit given)
+    recognized: int | None = None       # the single-feature classifier's class, 0..C-1 (None: not asked, or too small)
+    recognized_prob: float | None = None     # its softmax probability
+
+    @property
+    def agrees(self) -> bool | None:
+        """The classifier names the class the record carries: ``cls == recognized + 1`` (the label rule
+        of ``generate_parts``: label = 1 + class); None where the classifier was not asked."""
+        return None if self.recognized is None else self.cls == self.recognized + 1
 
     @property
     def clearance(self) -> float | None:
@@ -200,7 +208,8 @@ class FeatureInstance:
         (at ``min_fraction``), ``unreachable``, ``machinable`` and ``residual``; with contacts also
         ``wall_area``, ``open_area``, ``shared_area`` and ``floor`` (face -> faces), ``surface`` and
         ``neighbors`` (a list of ``{"id", "face", "faces"}``); with walls also ``gap2``, ``gap_at``,
-        ``gap_to``, ``min_wall`` (each None alone in the part) and ``thin_voxels``."""
+        ``gap_to``, ``min_wall`` (each None alone in the part) and ``thin_voxels``; with a classifier's
+        opinion also ``recognized``, ``recognized_prob`` and ``agrees``."""
         d = {"id": self.id, "class": self.cls, "voxels": self.voxels, "bbox": list(self.bbox),
              "centroid": list(self.centroid)}
         if self.access is not None:
@@ -222,11 +231,14 @@ class FeatureInstance:
         if self.walls:
             d.update(gap2=self.gap2, gap_at=None if self.gap_at is None else list(self.gap_at), gap_to=self.gap_to,
                      min_wall=self.min_wall, thin_voxels=self.thin_voxels)
+        if self.recognized is not None:
+            d.update(recognized=self.recognized, recognized_prob=self.recognized_prob, agrees=self.agrees)
         return d
 
     @staticmethod
     def from_table(table, offsets, min_voxels: int = 1, access=None, dims=None, shape=None, reach=None,
-                   tool=None, contacts=None, walls=None, thin: bool = True) -> "list[list[FeatureInstance]]":
+                   tool=None, contacts=None, walls=None, thin: bool = True,
+                   recognized=None) -> "list[list[FeatureInstance]]":
         """Per-sample record lists from an instance table int64 ``[T, 13]`` and its ``offsets``
         ``[N + 1]`` (tensors or arrays).  Components of fewer than ``min_voxels`` voxels are left
         out; the others keep their ``id``.  ``access``: the access table int64 ``[T, 8]`` of the
@@ -237,7 +249,9 @@ class FeatureInstance:
         ``[T, 19]`` of the same rows and its pair list int64 ``[P, 4]``, or None; a neighbour that
         ``min_voxels`` leaves out of the lists still appears in ``neighbors``, by its id.  ``walls``:
         the wall table int64 ``[T, 5]`` of the same rows, or None; it needs ``shape`` too, and with
-        ``thin=False`` (no limit was asked for) ``thin_voxels`` stays None."""
+        ``thin=False`` (no limit was asked for) ``thin_voxels`` stays None.  ``recognized``: ``(cls,
+        prob)`` of ``ops.isolate.recognize_table``, int64 and float32 ``[T]`` of the same rows, or None;
+        a row with ``cls < 0`` was not classified and keeps None."""
         tab = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.int64).reshape(-1, 13)
         off = np.asarray(offsets.cpu() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
         acc = None
@@ -283,6 +297,11 @@ class FeatureInstance:
             if shape is None or len(shape) != 3:
                 raise ValueError("from_table: walls needs shape = (D, H, W)")
             _, H, W = (int(s) for s in shape)
+        rec_cls = rec_prob = None
+        if recognized is not None:
+            rec_cls, rec_prob = (np.asarray(t.cpu() if hasattr(t, "cpu") else t).reshape(-1) for t in recognized)
+            if len(rec_cls) != len(tab) or len(rec_prob) != len(tab):
+                raise ValueError("from_table: the recognized classes do not belong to this instance table")
         out = []
         for n in range(len(off) - 1):
             recs = []
@@ -314,6 +333,8 @@ class FeatureInstance:
                     if gap2 >= 0:
                         rec.gap2, rec.gap_at = gap2, (at // (H * W), at // W % H, at % W)
                         rec.gap_to = other - int(off[n]) + 1
+                if rec_cls is not None and rec_cls[k] >= 0:
+                    rec.recognized, rec.recognized_prob = int(rec_cls[k]), float(rec_prob[k])
                 recs.append(rec)
             out.append(recs)
         return out
