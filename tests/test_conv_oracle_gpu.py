@@ -10,7 +10,7 @@ a sum listed in ``O.BOUNDED`` would get ``check_reduction``, but there is none, 
 tests/test_conv_oracle_cpu.py keeps that list honest.
 
 Guard bands: inputs sit in the middle of flat buffers whose ends hold a large finite sentinel
-(``O.banded``).  Every launch runs inside ``Guard``, which makes each device tensor the entry
+(``O.banded``).  Every launch runs inside ``Guard`` (tests/_guard.py), which makes each device tensor the entry
 point allocates -- outputs, statistics slabs, partial-sum scratch, packed weights -- the
 middle of a flat buffer too, its ends holding a known pattern and its middle NaN (``empty``)
 or zero (``zeros``); after the launch the bands of every such buffer still alive must be
@@ -24,8 +24,6 @@ more than one tile (over 8192 tiles) are not covered.
 """
 import functools
 import importlib
-import math
-import weakref
 
 import pytest
 import torch
@@ -34,6 +32,7 @@ pytestmark = pytest.mark.gpu
 
 import _conv_oracle as O  # noqa: E402
 from _bn_pool_oracle import ACT_TANH, bf16_round, check_exact, check_one_rounding, check_reduction  # noqa: E402
+from _guard import Guard, assert_guarded, launch  # noqa: E402
 from featurenet_amd import _native  # noqa: E402
 from featurenet_amd.ops import conv_tile as ct  # noqa: E402
 from featurenet_amd.ops import conv_wtile as cw  # noqa: E402
@@ -41,79 +40,6 @@ from featurenet_amd.ops import conv_wtile as cw  # noqa: E402
 C = importlib.import_module("featurenet_amd.ops.conv")
 NONE, RELU = O.ACT_NONE, O.ACT_RELU
 DEV = "cuda"
-
-
-# ---------------------------------------------------------------------------
-# guard bands around everything a launch allocates
-# ---------------------------------------------------------------------------
-_LIVE: list = []                                 # weak references to (flat buffer, payload elements)
-
-
-def _pattern(dtype, device):
-    return (torch.arange(O.BAND, device=device) % 119 + 1).to(dtype)
-
-
-class Guard:
-    def __enter__(self):
-        self._empty, self._zeros = torch.empty, torch.zeros
-        torch.empty, torch.zeros = self._alloc(False), self._alloc(True)
-        return self
-
-    def __exit__(self, et, ev, tb):
-        torch.empty, torch.zeros = self._empty, self._zeros
-        if et is None:
-            check_bands()
-
-    def _alloc(self, zero):
-        real = self._zeros if zero else self._empty
-
-        def alloc(*size, dtype=None, device=None, **kw):
-            if kw or device is None or torch.device(device).type != "cuda":
-                return real(*size, dtype=dtype, device=device, **kw)
-            shape = tuple(size[0]) if len(size) == 1 and not isinstance(size[0], int) else tuple(size)
-            dtype = dtype or torch.get_default_dtype()
-            n = math.prod(shape)
-            flat = self._empty(n + 2 * O.BAND, dtype=dtype, device=device)
-            flat[: O.BAND] = _pattern(dtype, device)
-            flat[O.BAND + n:] = _pattern(dtype, device)
-            mid = flat[O.BAND: O.BAND + n]
-            mid.fill_(0 if zero or not dtype.is_floating_point else float("nan"))
-            _LIVE.append((weakref.ref(flat), n))
-            return mid.view(shape)
-
-        return alloc
-
-
-def check_bands():
-    """After a launch: no band of any guarded buffer that is still in use has changed."""
-    torch.cuda.synchronize()
-    keep = []
-    for ref, n in _LIVE:
-        flat = ref()
-        if flat is None:
-            continue
-        keep.append((ref, n))
-        pat = _pattern(flat.dtype, flat.device)
-        assert torch.equal(flat[: O.BAND], pat), f"a launch wrote in front of a {flat.dtype} buffer of {n}"
-        assert torch.equal(flat[O.BAND + n:], pat), f"a launch wrote behind a {flat.dtype} buffer of {n}"
-    _LIVE[:] = keep
-
-
-def assert_guarded(out):
-    """Every device tensor an entry point returned lives in a guarded buffer (an allocation that
-    went past ``Guard`` -- ``empty_like``, ``new_empty``, C++ -- would have no bands to check)."""
-    live = {f.untyped_storage().data_ptr() for f in (ref() for ref, _ in _LIVE) if f is not None}
-    for t in (out if isinstance(out, (tuple, list)) else (out,)):
-        if isinstance(t, torch.Tensor) and t.is_cuda:
-            assert t.untyped_storage().data_ptr() in live, f"an output of {tuple(t.shape)} was allocated outside the guard"
-
-
-def launch(fn):
-    """One entry-point call inside the guard bands."""
-    with Guard():
-        out = fn()
-        assert_guarded(out)
-    return out
 
 
 # ---------------------------------------------------------------------------
