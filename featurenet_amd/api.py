@@ -399,7 +399,7 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
 @torch.no_grad()
 def label_components(labels, background: int | None = 0, connectivity: int = 6, device=None, occupancy=None,
                      dimensions: bool = False, tool=None, contacts: bool = False, walls=False, classifier=None,
-                     min_voxels: int = 1, batch_size: int = 256):
+                     min_voxels: int = 1, batch_size: int = 256, split=None):
     """Connected components of label volumes the caller already has (ground truth, say) ->
     (ids int32 [N, D, H, W], one list of :class:`FeatureInstance` per sample).
 
@@ -417,10 +417,16 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     classifier's ``recognized`` / ``recognized_prob`` as its ``classifier`` does: the grid is resampled
     to the classifier's input size, ``batch_size`` parts run at a time, and components of fewer than
     ``min_voxels`` voxels are not classified -- they stay in the lists with ``recognized = None``.
+    ``split`` (a merge height in voxels, a multiple of 0.5; it needs ``occupancy``) cuts every component
+    along the passes of the distance to the material before anything else is computed, as
+    :func:`split_features` does: the ids, the records and every table are those of the pieces, which keep
+    their component's class and carry ``component`` and ``peak2``.  None leaves every result as it is.
     """
     from .ops import ccl
     from .utils.seginstances import FeatureInstance, tool_thresholds
 
+    if split is not None and occupancy is None:
+        raise ValueError("label_components(): split needs occupancy (the material the passes are measured against)")
     if dimensions and occupancy is None:
         raise ValueError("label_components(): dimensions=True needs occupancy (the material the widths are "
                          "measured against)")
@@ -456,7 +462,8 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
     roots, flags = ccl.connected_components(lt, background, connectivity, return_flags=True)
     ids, table, offsets = ccl.instance_table(lt, roots, want_ids=True, flags=flags)
     occ = None if ot is None else (ot.to(device) != 0).to(torch.uint8)
-    more = _geometry_tables(ids, table, offsets, occ, occ is not None, dimensions, thresholds, contacts, limit2)
+    ids, table, offsets, cut, d2 = _split(ids, table, offsets, occ, split)
+    more = _geometry_tables(ids, table, offsets, occ, occ is not None, dimensions, thresholds, contacts, limit2, d2=d2)
     seen = None
     if classifier is not None:
         from .ops import isolate
@@ -464,21 +471,39 @@ def label_components(labels, background: int | None = 0, connectivity: int = 6, 
         seen = isolate.recognize_table(classifier, ids, table, offsets, rows=table.shape[0], min_voxels=min_voxels,
                                        batch_size=batch_size)[:2]
     return ids.cpu().numpy(), FeatureInstance.from_table(table, offsets, shape=tuple(lt.shape[1:]), tool=thresholds,
-                                                         thin=walls is not True, recognized=seen, **more)
+                                                         thin=walls is not True, recognized=seen, split=cut, **more)
 
 
-def _geometry_tables(ids, table, offsets, occ, access: bool, dimensions: bool, thresholds, contacts: bool, limit2):
+def _split(ids, table, offsets, occ, split):
+    """The ``split`` option of :func:`label_components` and :func:`recognize` -> ``(ids, table, offsets, (component,
+    peak2) or None, d2 or None)``: with a merge height every component is cut by ``ops.watershed`` on ``d2 =
+    distance_sq(occ)``, and a piece keeps its component's class; None passes everything through."""
+    if split is None:
+        return ids, table, offsets, None, None
+    from .ops import edt, watershed
+
+    d2 = edt.distance_sq(occ)
+    ids2, table2, offsets2, comp, peak2 = watershed.split_instances(ids, d2, split)
+    if len(table2):
+        table2[:, 1] = table[offsets[table2[:, 0]] + comp - 1, 1]
+    return ids2, table2, offsets2, (comp, peak2), d2
+
+
+def _geometry_tables(ids, table, offsets, occ, access: bool, dimensions: bool, thresholds, contacts: bool, limit2,
+                     d2=None):
     """The optional tables of an id volume as keyword arguments of ``FeatureInstance.from_table``
     (``access``, ``dims``, ``reach``, ``contacts``, ``walls``), each None where it is not asked for.
-    Everything but ``walls`` needs the occupancy ``occ``."""
+    Everything but ``walls`` needs the occupancy ``occ``.  ``d2``: ``edt.distance_sq(occ)`` where a split has
+    computed it already."""
     from .ops import access as access_, contact, edt, nearest, reach
 
-    acc = dim = rch = d2 = pairs = wall = None
+    acc = dim = rch = pairs = wall = None
     T = table.shape[0]
     if access:
         acc, _ = access_.access_table(ids, offsets, occ, rows=T)
     if dimensions:
-        dim, d2 = edt.dimension_table(ids, offsets, occ, rows=T, want_d2=thresholds is not None)
+        dim, d2 = edt.dimension_table(ids, offsets, occ, rows=T, want_d2=thresholds is not None or d2 is not None,
+                                      d2=d2)
     if thresholds is not None:
         rch, _ = reach.reach_table(ids, offsets, occ, *thresholds, rows=T, d2=d2)
     if contacts:
@@ -584,7 +609,8 @@ def isolate_features(ids, features=None, size: int | None = None, occupancy=None
 @torch.no_grad()
 def recognize(classifier, voxels, stock: str = "grid", connectivity: int = 6, min_voxels: int = 1,
               return_ids: bool = False, return_labels: bool = False, batch_size: int = 256, device=None,
-              access: bool = False, dimensions: bool = False, tool=None, contacts: bool = False, walls=False):
+              access: bool = False, dimensions: bool = False, tool=None, contacts: bool = False, walls=False,
+              split=None):
     """The features of each part by the single-feature classifier alone, the multi-feature recipe of
     the FeatureNet paper -> ``(features, ids or None, labels or None)``: one list of
     :class:`FeatureInstance` per sample, ids int32 ``[N, D, H, W]`` with ``return_ids`` and labels
@@ -600,9 +626,12 @@ def recognize(classifier, voxels, stock: str = "grid", connectivity: int = 6, mi
     of :func:`generate_parts`, so the records compare with those of a segmentation model; ``labels``
     holds that ``cls`` on every voxel of the component and 0 elsewhere, ready for
     :func:`match_features`.  Components of fewer than ``min_voxels`` voxels are left out of the lists
-    and of ``labels``; ``ids`` keeps them.  Features that touch are one component here: without a
-    segmentation model nothing tells them apart.  ``access``, ``dimensions``, ``tool``, ``contacts``
-    and ``walls`` as for :func:`extract_features`.
+    and of ``labels``; ``ids`` keeps them.  Features that touch are one component; ``split`` (a merge
+    height in voxels, a multiple of 0.5; the paper's watershed step) cuts each component along the passes
+    of the distance to the material before it is isolated and classified, as :func:`split_features` does
+    -- a hole in a pocket floor then becomes a record of its own, with ``component`` and ``peak2`` -- and
+    None leaves touching features as one.  ``access``, ``dimensions``, ``tool``, ``contacts`` and
+    ``walls`` as for :func:`extract_features`; with ``split`` they describe the pieces.
     """
     from .ops import ccl, isolate
     from .utils.seginstances import FeatureInstance, tool_thresholds
@@ -628,20 +657,74 @@ def recognize(classifier, voxels, stock: str = "grid", connectivity: int = 6, mi
     removed = removed.to(torch.uint8)
     roots, flags = ccl.connected_components(removed, 0, connectivity, return_flags=True)
     ids, table, offsets = ccl.instance_table(removed, roots, want_ids=True, flags=flags)
+    ids, table, offsets, cut, d2 = _split(ids, table, offsets, occ, split)
     T = table.shape[0]
     cls, prob, _ = isolate.recognize_table(classifier, ids, table, offsets, rows=T, min_voxels=min_voxels,
                                            window=window, batch_size=batch_size)
     table = table.clone()
     table[:, 1] = cls + 1
-    more = _geometry_tables(ids, table, offsets, occ, access, dimensions, thresholds, contacts, limit2)
+    more = _geometry_tables(ids, table, offsets, occ, access, dimensions, thresholds, contacts, limit2, d2=d2)
     feats = FeatureInstance.from_table(table, offsets, min_voxels, shape=tuple(occ.shape[1:]), tool=thresholds,
-                                       thin=walls is not True, recognized=(cls, prob), **more)
+                                       thin=walls is not True, recognized=(cls, prob), split=cut, **more)
     labels = None
     if return_labels:
         lut = torch.cat([table.new_zeros(1), table[:, 1]])                      # 0: no component
         row = torch.where(ids > 0, ids.to(torch.int64) + offsets[:-1].view(-1, 1, 1, 1), 0)
         labels = lut[row].to(torch.uint8).cpu().numpy()
     return feats, (ids.cpu().numpy() if return_ids else None), labels
+
+
+@torch.no_grad()
+def split_features(ids, occupancy=None, height=None, merge=1.0, device=None):
+    """Touching features told apart by a watershed on the distance to the material -> ``(ids, features)``: ids
+    int32 ``[N, D, H, W]`` and one list of :class:`FeatureInstance` per sample.
+
+    ``ids`` is ``[N, D, H, W]`` of an integer dtype, as :func:`label_components`, :func:`extract_features`
+    (``return_ids``) and :func:`recognize` give it: a voxel ``> 0`` belongs to the component of that number in
+    its sample; every axis is at most 256.  Exactly one of ``occupancy`` (integers or bools of the ids' shape,
+    non-zero: material; the height is then :func:`distance_transform` of it, squared distances) and ``height``
+    (integers of the ids' shape, below 2^31; negative values count as 0) is given.  Inside each component every
+    voxel climbs to its highest 26-neighbour until it reaches a peak; the voxels of one peak are a basin, two
+    basins that touch are joined over their highest pass, and they become one feature when the lower of the two
+    peaks rises less than ``merge`` voxels of clearance above that pass: ``sqrt(peak2) - sqrt(saddle2) <= merge /
+    2``, decided in integers.  ``merge`` is a multiple of 0.5, ``>= 0``: 0 joins only what is equally high,
+    larger values join more, and a height that is constant gives the components back.  The new ids number the
+    features of a sample from 1; a record has ``cls = 1``, ``component`` (the id it was cut from) and ``peak2``.
+    ``device`` defaults to the GPU when there is one (the ``watershed`` kernels), else the CPU reference path;
+    the result is the same.
+    """
+    from .ops import edt, watershed
+    from .utils.seginstances import FeatureInstance
+
+    if (occupancy is None) == (height is None):
+        raise ValueError("split_features(): give exactly one of occupancy and height")
+    it = torch.as_tensor(np.asarray(ids)) if not isinstance(ids, torch.Tensor) else ids
+    if it.is_floating_point() or it.is_complex() or it.dtype == torch.bool:
+        raise ValueError(f"split_features(): ids must be integers, not {it.dtype}")
+    if it.dim() != 4:
+        raise ValueError(f"split_features(): ids must be [N, D, H, W], not {tuple(it.shape)}")
+    if it.dtype != torch.int32 and it.numel() and int(it.max()) >= 1 << 31:
+        raise ValueError("split_features(): ids must be below 2^31")
+    watershed.merge_steps(merge)
+    src = occupancy if height is None else height
+    name = "occupancy" if height is None else "height"
+    st = torch.as_tensor(np.asarray(src)) if not isinstance(src, torch.Tensor) else src
+    if st.is_floating_point() or st.is_complex() or (height is not None and st.dtype == torch.bool):
+        raise ValueError(f"split_features(): {name} must be integers{' or bools' if height is None else ''}, not "
+                         f"{st.dtype}")
+    if st.shape != it.shape:
+        raise ValueError(f"split_features(): {name} is {tuple(st.shape)} but ids {tuple(it.shape)}")
+    if height is not None and st.dtype != torch.int32 and st.numel() and int(st.max()) >= 1 << 31:
+        raise ValueError("split_features(): height must be below 2^31")
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    it = it.to(device).clamp(min=0).to(torch.int32).contiguous()
+    if height is None:
+        h = edt.distance_sq((st.to(device) != 0).to(torch.uint8))
+    else:
+        h = st.to(device).clamp(min=0).to(torch.int32).contiguous()
+    out, table, offsets, comp, peak2 = watershed.split_instances(it, h, merge)
+    return out.cpu().numpy(), FeatureInstance.from_table(table, offsets, split=(comp, peak2))
 
 
 def _wall_limit(walls):

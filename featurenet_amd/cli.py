@@ -17,6 +17,7 @@ segment    per-voxel labels of a segmentation checkpoint -> .npy
 score      confusion matrix / per-class IoU / mIoU of a segmentation checkpoint against true labels
 features   the feature instances (connected components of the labels) of a segmentation checkpoint -> JSON
 recognize  the features of multi-feature parts by a single-feature classifier checkpoint alone -> JSON
+split      touching features of an instance-id volume told apart by a watershed on the distance to the material
 score-features
            predicted features matched to the true ones: per-class TP / FP / FN, F1 and panoptic quality
 generate-parts
@@ -269,11 +270,28 @@ def cmd_recognize(a) -> int:
     feats, ids, labels = api.recognize(a.model, x, stock=a.stock, connectivity=a.connectivity,
                                        min_voxels=a.min_voxels, return_ids=bool(a.ids), return_labels=bool(a.labels),
                                        device=a.device or None, access=a.access, dimensions=a.dimensions, tool=a.tool,
-                                       contacts=a.contacts, walls=False if a.walls is None else a.walls)
+                                       contacts=a.contacts, walls=False if a.walls is None else a.walls, split=a.split)
     if a.ids:
         np.save(a.ids, ids)
     if a.labels:
         np.save(a.labels, labels)
+    summary = json.dumps({"samples": [[f.to_dict() for f in fs] for fs in feats]})
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(summary + "\n")
+    print(summary)
+    return 0
+
+
+def cmd_split(a) -> int:
+    import numpy as np
+
+    from . import api
+
+    ids = np.load(a.ids, allow_pickle=False)
+    vox = np.load(a.voxels, allow_pickle=False)
+    out, feats = api.split_features(ids, occupancy=vox, merge=a.merge, device=a.device or None)
+    np.save(a.output, out)
     summary = json.dumps({"samples": [[f.to_dict() for f in fs] for fs in feats]})
     if a.json:
         with open(a.json, "w") as f:
@@ -628,7 +646,24 @@ def build_parser() -> argparse.ArgumentParser:
     rg.add_argument("--tool", type=float, default=None, metavar="T", help="as for features")
     rg.add_argument("--contacts", action="store_true", help="as for features")
     rg.add_argument("--walls", type=float, nargs="?", const=True, default=None, metavar="T", help="as for features")
+    rg.add_argument("--split", type=float, nargs="?", const=1.0, default=None, metavar="H",
+                    help="cut touching features apart first (a watershed on the distance to the material); two "
+                         "peaks stay one feature when the lower rises less than H voxels of clearance above the pass "
+                         "between them (a multiple of 0.5, default 1); adds component and peak2")
     rg.set_defaults(fn=cmd_recognize)
+
+    sp = sub.add_parser("split", help="touching features told apart: each component of an instance-id volume cut "
+                                      "along the passes of the distance to the material -> int32 .npy and JSON")
+    sp.add_argument("ids", help="[N, D, H, W] integer instance ids (.npy), > 0 = a component's voxel, each axis at "
+                                "most 256")
+    sp.add_argument("voxels", help="[N, D, H, W] occupancy (.npy), non-zero = material")
+    sp.add_argument("-o", "--output", required=True, help="the new instance ids, int32, the input's shape (.npy)")
+    sp.add_argument("--merge", type=float, default=1.0, metavar="H",
+                    help="two peaks stay one feature when the lower rises less than H voxels of clearance above the "
+                         "pass between them (a multiple of 0.5, default 1)")
+    sp.add_argument("--device", default="", help="cuda / cpu (default: the GPU when there is one)")
+    sp.add_argument("--json", default="", metavar="OUT", help="also write the JSON document to this file")
+    sp.set_defaults(fn=cmd_split)
 
     nr = sub.add_parser("nearest", help="labelled distance transform: the nearest and the nearest other instance of "
                                         "every voxel with their squared distances -> .npz (d2, nearest)")

@@ -70,6 +70,11 @@ int fn_isolate_parts(const void*, const void*, void*, int, int, int, int, long l
 void fn_contact_chunk(int*);
 int fn_contact_stats(const void*, const void*, const void*, void*, void*, void*, void*, int, int, int, int, long long,
                      long long, long long, hipStream_t);
+void fn_ws_tile(int*);
+int fn_ws_ascend(const void*, const void*, void*, int, int, int, int, int, hipStream_t);
+int fn_ws_resolve(const void*, void*, void*, int, int, int, int, hipStream_t);
+int fn_ws_saddle(const void*, const void*, const void*, const void*, void*, void*, void*, int, int, int, int, long long,
+                 long long, long long, hipStream_t);
 int fn_pw_wgrad(const void*, const void*, float*, long long, int, int, hipStream_t, const float*, const float*, int,
                 float*);
 int fn_pw_wgrad_blocks(long long, int, int);
@@ -917,6 +922,55 @@ PYBIND11_MODULE(_C, m) {
                          P<void*>(keys), P<void*>(counts), P<void*>(lost), N, D, H, W, T, cap, probe, S(st)),
         "contact_stats");
   }, py::arg("ids"), py::arg("occ"), py::arg("offsets"), py::arg("contact"), py::arg("keys"), py::arg("counts"),
+     py::arg("lost"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("T"), py::arg("cap"),
+     py::arg("probe"), py::arg("st"), py::arg("ext"));
+  // watershed split of touching instances (watershed.hip): ids and height int32 [N][D][H][W], D, H, W <= 256 and
+  // N*D*H*W < 2^31; parent int32 of that shape: 1 + the index in the sample of the 26-neighbour of the same id with
+  // the largest (max(height, 0), lowest index) when that beats the voxel's own, else of the voxel, 0 where ids <= 0;
+  // staged 1: the LDS tile kernel, 0: the plain one; ext = {numel(ids), numel(height), numel(parent)}
+  m.def("ws_tile", []() {
+    int t[5];
+    fn_ws_tile(t);
+    return py::make_tuple(t[0], t[1], t[2], t[3], t[4]);
+  });
+  m.def("ws_ascend", [](uintptr_t ids, uintptr_t height, uintptr_t parent, int N, int D, int H, int W, int staged,
+                        uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "ws_ascend", "ids");
+    fits(ext, 1, prod({N, D, H, W}), "ws_ascend", "height");
+    fits(ext, 2, prod({N, D, H, W}), "ws_ascend", "parent");
+    chk(fn_ws_ascend(P<const void*>(ids), P<const void*>(height), P<void*>(parent), N, D, H, W, staged, S(st)),
+        "ws_ascend");
+  }, py::arg("ids"), py::arg("height"), py::arg("parent"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"),
+     py::arg("staged"), py::arg("st"), py::arg("ext"));
+  // roots int32: 1 + the end of each voxel's chain of parents (0: no id, or a word that is no parent pointer on
+  // the way), flags int32: roots[v] == v + 1; both written in full; ext = {numel(parent), numel(roots), numel(flags)}
+  m.def("ws_resolve", [](uintptr_t parent, uintptr_t roots, uintptr_t flags, int N, int D, int H, int W, uintptr_t st,
+                         std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "ws_resolve", "parent");
+    fits(ext, 1, prod({N, D, H, W}), "ws_resolve", "roots");
+    fits(ext, 2, prod({N, D, H, W}), "ws_resolve", "flags");
+    chk(fn_ws_resolve(P<const void*>(parent), P<void*>(roots), P<void*>(flags), N, D, H, W, S(st)), "ws_resolve");
+  }, py::arg("parent"), py::arg("roots"), py::arg("flags"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"),
+     py::arg("st"), py::arg("ext"));
+  // bids int32 [N*V] and offsets int64 [N+1]: the basin ids and the basin table's offsets (T rows); keys uint64
+  // [cap] / counts int64 [cap] / lost int64 [1]: the pair table of overlap_pairs under the key row_lo << 32 | row_hi
+  // (1-based rows), counts the largest min(height, height) over the adjacent voxel pairs of the two basins inside
+  // one component, lost the updates that found no slot; keys, counts and lost are zero on entry; ext = {numel(ids),
+  // numel(bids), numel(offsets), numel(height), numel(keys), numel(counts), numel(lost)}
+  m.def("ws_saddle", [](uintptr_t ids, uintptr_t bids, uintptr_t offsets, uintptr_t height, uintptr_t keys,
+                        uintptr_t counts, uintptr_t lost, int N, int D, int H, int W, long long T, long long cap,
+                        long long probe, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({N, D, H, W}), "ws_saddle", "ids");
+    fits(ext, 1, prod({N, D, H, W}), "ws_saddle", "bids");
+    fits(ext, 2, N < 0 ? -1 : N + 1LL, "ws_saddle", "offsets");
+    fits(ext, 3, prod({N, D, H, W}), "ws_saddle", "height");
+    fits(ext, 4, cap, "ws_saddle", "keys");
+    fits(ext, 5, cap, "ws_saddle", "counts");
+    fits(ext, 6, 1, "ws_saddle", "lost");
+    chk(fn_ws_saddle(P<const void*>(ids), P<const void*>(bids), P<const void*>(offsets), P<const void*>(height),
+                     P<void*>(keys), P<void*>(counts), P<void*>(lost), N, D, H, W, T, cap, probe, S(st)),
+        "ws_saddle");
+  }, py::arg("ids"), py::arg("bids"), py::arg("offsets"), py::arg("height"), py::arg("keys"), py::arg("counts"),
      py::arg("lost"), py::arg("N"), py::arg("D"), py::arg("H"), py::arg("W"), py::arg("T"), py::arg("cap"),
      py::arg("probe"), py::arg("st"), py::arg("ext"));
   // each selected instance alone in a solid stock block (isolate.hip): ids int32 [N][D][H][W], D, H, W <= 256 and

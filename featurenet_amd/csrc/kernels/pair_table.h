@@ -60,6 +60,39 @@ __device__ __forceinline__ bool pt_stage_add(unsigned long long* s_key, unsigned
   return met;
 }
 
+// The max forms (ws_saddle_kernel, watershed.hip): counts[slot of key] = max(counts[slot of key], val) for val >=
+// 0 over the caller's zeros -- the key, not the value, says that a slot is held, so a largest value of 0 stays a
+// row.  A maximum does not depend on the order of the atomics either.  A dropped update adds 1 to lost[0].
+__device__ __forceinline__ void pt_global_max(unsigned long long* keys, long long* counts, long long* lost,
+                                              unsigned long long mask, long long bound, unsigned long long key,
+                                              long long val) {
+  unsigned long long h = pt_mix(key) & mask;
+  for (long long i = 0; i < bound; ++i) {
+    unsigned long long held = 0;
+    __hip_atomic_compare_exchange_strong(&keys[h], &held, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+    if (held == 0 || held == key) {
+      __hip_atomic_fetch_max(&counts[h], val, IP_RLX_AGENT);
+      return;
+    }
+    h = (h + 1) & mask;
+  }
+  __hip_atomic_fetch_add(lost, 1LL, IP_RLX_AGENT);
+}
+
+__device__ __forceinline__ bool pt_stage_max(unsigned long long* s_key, unsigned long long* s_val,
+                                             unsigned long long key, unsigned long long val) {
+  int slot = (int)(pt_mix(key) >> 55) & (IP_SLOTS - 1);
+  bool met = false;
+  for (int p = 0; p < PT_LPROBE && !met; ++p) {
+    const unsigned long long held = atomicCAS(&s_key[slot], 0ull, key);
+    met = held == 0 || held == key;
+    if (met) atomicMax(&s_val[slot], val);
+    slot = (slot + 1) & (IP_SLOTS - 1);
+  }
+  return met;
+}
+
 // cap: a power of two in [2, 2^32]; probe >= 1
 static inline bool pt_shape_ok(long long cap, long long probe) {
   return cap >= 2 && cap <= (1LL << 32) && (cap & (cap - 1)) == 0 && probe >= 1;

@@ -46,21 +46,24 @@ def distance_sq(seeds: torch.Tensor, border: bool = False) -> torch.Tensor:
 
 
 def dimension_table(ids: torch.Tensor, offsets: torch.Tensor, occ: torch.Tensor, rows: int | None = None,
-                    want_d2: bool = False):
+                    want_d2: bool = False, d2: torch.Tensor | None = None):
     """``(dim, d2 or None)`` of an id volume, its instance table's ``offsets`` and the occupancy:
     dim int64 ``[T, 4]`` = ``r2, at, wall, voxels`` (``reference.dimension_table`` over
     ``distance_sq(occ)``: the material is the seed, the grid's border is not), d2 int32 ``[N, D, H,
     W]``, on the ids' device.  ``rows``: the table's row count ``T = offsets[-1]`` when the caller
-    knows it (it saves the device-to-host read that sizes the table)."""
+    knows it (it saves the device-to-host read that sizes the table).  ``d2``: ``distance_sq(occ)`` when the
+    caller already has it."""
     _check_seeds(occ, "dimension_table", "occ")
     check_ids_offsets(ids, offsets, occ, "dimension_table")
+    if d2 is not None and (d2.shape != occ.shape or d2.dtype != torch.int32 or d2.device != occ.device):
+        raise ValueError(f"dimension_table: d2 must be int32 {tuple(occ.shape)} on {occ.device}")
     if not _native.use_native(ids) or ids.numel() == 0:
-        d2 = reference.distance_sq(occ)
+        d2 = reference.distance_sq(occ) if d2 is None else d2
         return reference.dimension_table(ids, offsets, d2), (d2 if want_d2 else None)
     check_batch(ids, "dimension_table")
     ids, offsets = ids.contiguous(), offsets.contiguous()
     N, D, H, W = ids.shape
-    d2 = distance_sq(occ)
+    d2 = distance_sq(occ) if d2 is None else d2.contiguous()
     T = int(offsets[-1]) if rows is None else int(rows)
     raw = torch.empty(T, 3, dtype=torch.int64, device=ids.device)
     _native.kernels().edt_stats(ids.data_ptr(), offsets.data_ptr(), d2.data_ptr(), raw.data_ptr(), N, D, H, W, T,

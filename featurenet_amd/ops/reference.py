@@ -875,3 +875,109 @@ def isolate_instances(ids: torch.Tensor, sel: torch.Tensor, size: int, fmt: int 
         return out.to(torch.bfloat16).unsqueeze(-1)
     weights = 1 << torch.arange(8, dtype=torch.int32, device=dev)
     return (out.reshape(M, S ** 3 // 8, 8).to(torch.int32) * weights).sum(-1).to(torch.uint8)
+
+
+WS_MAX_S = 256             # longest axis the watershed takes
+
+
+def _ws_check(ids: torch.Tensor, height: torch.Tensor, what: str) -> None:
+    if ids.dim() != 4 or ids.dtype != torch.int32:
+        raise ValueError(f"{what}: ids must be int32 [N, D, H, W], not {ids.dtype} {tuple(ids.shape)}")
+    if height.shape != ids.shape or height.dtype != torch.int32 or height.device != ids.device:
+        raise ValueError(f"{what}: height must be int32 {tuple(ids.shape)} on {ids.device}, not {height.dtype} "
+                         f"{tuple(height.shape)} on {height.device}")
+    if max(ids.shape[1:]) > WS_MAX_S:
+        raise ValueError(f"{what}: each of D, H, W is at most {WS_MAX_S}, not {tuple(ids.shape[1:])}")
+
+
+def _ws_shifts(D: int, H: int, W: int, forward: bool):
+    """``(dst, src)`` slices of ``[N, D, H, W]`` for the 26 offsets (the 13 with ``(dz, dy, dx) > (0, 0, 0)`` when
+    ``forward``): voxel ``dst`` has its neighbour at that offset in ``src``."""
+    for dz, dy, dx in _ccl_offsets(26):
+        if forward and (dz, dy, dx) < (0, 0, 0):
+            continue
+
+        def sl(n, d):
+            return (slice(max(0, -d), n - max(0, d)), slice(max(0, d), n - max(0, -d)))
+        (zd, zs), (yd, ys), (xd, xs) = sl(D, dz), sl(H, dy), sl(W, dx)
+        yield (slice(None), zd, yd, xd), (slice(None), zs, ys, xs)
+
+
+def watershed_parents(ids: torch.Tensor, height: torch.Tensor) -> torch.Tensor:
+    """One step of the steepest ascent inside the components of an id volume -> ``parent`` int32 ``[N, D, H, W]``.
+
+    ``ids`` int32 ``[N, D, H, W]`` (a voxel with ``ids > 0`` belongs to that component of its sample) and
+    ``height`` int32 of the same shape, ``h(v) = max(height[v], 0)``.  ``key(v) = h(v) << 32 | (0xFFFFFFFF -
+    index of v in its sample)``: the higher voxel wins, then the lower index.  ``u`` is a neighbour of ``v``
+    when it is one of its 26 neighbours in the grid and the sample and ``ids[u] == ids[v]``; ``parent[v]`` is 1
+    + the index of the neighbour of the largest key when that key exceeds ``key(v)``, else of ``v`` itself, and 0
+    where ``ids <= 0``.  Each axis is at most ``WS_MAX_S``.  One maximum over 26 shifted views: the oracle of
+    ``ws_ascend``."""
+    _ws_check(ids, height, "watershed_parents")
+    N, D, H, W = ids.shape
+    V, dev = D * H * W, ids.device
+    if N * V == 0:
+        return torch.zeros_like(ids)
+    lin = torch.arange(V, device=dev).view(1, D, H, W)
+    key = height.clamp(min=0).to(torch.int64) << 32 | (0xFFFFFFFF - lin)
+    fg = ids > 0
+    best = key.clone()
+    for dst, src in _ws_shifts(D, H, W, False):
+        ok = fg[dst] & (ids[dst] == ids[src])
+        best[dst] = torch.where(ok, torch.maximum(best[dst], key[src]), best[dst])
+    return torch.where(fg, 0xFFFFFFFF - (best & 0xFFFFFFFF) + 1, 0).to(torch.int32)
+
+
+def watershed_ascend(ids: torch.Tensor, height: torch.Tensor) -> torch.Tensor:
+    """Steepest ascent inside the components of an id volume -> ``roots`` int32 ``[N, D, H, W]``: 1 + the index
+    of the end of every voxel's chain of :func:`watershed_parents` (keys are distinct and grow along it, so it
+    ends), 0 where ``ids <= 0``.  The voxels of one root are a *basin*, and a root has ``roots[v] == v + 1``.
+
+    Pointer doubling over the parents to a fixed point: the oracle of ``ws_ascend`` + ``ws_resolve`` and the CPU
+    path of ``ops.watershed.ascend``."""
+    parent = watershed_parents(ids, height)
+    N, V = ids.shape[0], ids[0].numel() if ids.shape[0] else 0
+    if N * V == 0:
+        return parent
+    lin = torch.arange(V, device=ids.device).expand(N, V)
+    p = torch.where(parent.view(N, V) > 0, parent.view(N, V).to(torch.int64) - 1, lin)
+    while True:
+        q = p.gather(1, p)
+        if torch.equal(q, p):
+            break
+        p = q
+    return torch.where(ids > 0, p.view(ids.shape) + 1, 0).to(torch.int32)
+
+
+def watershed_saddles(ids: torch.Tensor, basin_ids: torch.Tensor, offsets: torch.Tensor,
+                      height: torch.Tensor) -> torch.Tensor:
+    """Saddles between the basins of each component -> ``pairs`` int64 ``[P, 3]``.
+
+    ``ids`` and ``height`` as for :func:`watershed_ascend`; ``basin_ids`` int32 of the same shape and ``offsets``
+    int64 ``[N + 1]`` as :func:`instance_table` gives them over the watershed's roots (``T = offsets[-1]``).  Over
+    every pair ``(u, v)`` of 26-adjacent voxels of one sample with ``ids[u] == ids[v] > 0`` whose basin rows
+    ``offsets[n] + basin_ids - 1`` both lie in the table and differ, ``saddle(a, b)`` is the largest ``min(h(u),
+    h(v))`` between the rows ``a`` and ``b``.  One row ``(row_a, row_b, saddle)`` per pair of rows that occurs,
+    0-based with ``row_a < row_b``, sorted by ``(row_a, row_b)``.  Shifted views, ``torch.unique`` and a scatter
+    maximum: the oracle of ``ws_saddle`` and the CPU path of ``ops.watershed.saddle_pairs``."""
+    _ws_check(ids, height, "watershed_saddles")
+    N, D, H, W = ids.shape
+    dev = ids.device
+    T = int(offsets[-1])
+    none = torch.zeros(0, 3, dtype=torch.int64, device=dev)
+    if T == 0 or ids.numel() == 0:
+        return none
+    row = basin_ids.to(torch.int64) + offsets.to(torch.int64)[:-1].view(N, 1, 1, 1) - 1
+    live = (ids > 0) & (basin_ids > 0) & (row >= 0) & (row < T)
+    h = height.clamp(min=0).to(torch.int64)
+    keys, vals = [], []
+    for dst, src in _ws_shifts(D, H, W, True):
+        ok = live[dst] & live[src] & (ids[dst] == ids[src]) & (row[dst] != row[src])
+        a, b = row[dst][ok], row[src][ok]
+        keys.append(torch.minimum(a, b) << 32 | torch.maximum(a, b))
+        vals.append(torch.minimum(h[dst][ok], h[src][ok]))
+    key, which = torch.unique(torch.cat(keys), return_inverse=True)
+    if key.numel() == 0:
+        return none
+    saddle = torch.full_like(key, -1).scatter_reduce(0, which, torch.cat(vals), "amax")
+    return torch.stack([key >> 32, key & 0xFFFFFFFF, saddle], 1)

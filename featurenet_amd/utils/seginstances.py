@@ -93,6 +93,8 @@ class FeatureInstance:
     thin_voxels: int | None = None      # its voxels with another instance within the wall limit (None: no limit given)
     recognized: int | None = None       # the single-feature classifier's class, 0..C-1 (None: not asked, or too small)
     recognized_prob: float | None = None     # its softmax probability
+    component: int | None = None   # the id of the connected component a watershed split cut it from (None: no split)
+    peak2: int | None = None       # the largest squared distance to the material inside it, as the split saw it
 
     @property
     def agrees(self) -> bool | None:
@@ -209,7 +211,8 @@ class FeatureInstance:
         ``wall_area``, ``open_area``, ``shared_area`` and ``floor`` (face -> faces), ``surface`` and
         ``neighbors`` (a list of ``{"id", "face", "faces"}``); with walls also ``gap2``, ``gap_at``,
         ``gap_to``, ``min_wall`` (each None alone in the part) and ``thin_voxels``; with a classifier's
-        opinion also ``recognized``, ``recognized_prob`` and ``agrees``."""
+        opinion also ``recognized``, ``recognized_prob`` and ``agrees``; after a watershed split also
+        ``component`` and ``peak2``."""
         d = {"id": self.id, "class": self.cls, "voxels": self.voxels, "bbox": list(self.bbox),
              "centroid": list(self.centroid)}
         if self.access is not None:
@@ -233,12 +236,14 @@ class FeatureInstance:
                      min_wall=self.min_wall, thin_voxels=self.thin_voxels)
         if self.recognized is not None:
             d.update(recognized=self.recognized, recognized_prob=self.recognized_prob, agrees=self.agrees)
+        if self.component is not None:
+            d.update(component=self.component, peak2=self.peak2)
         return d
 
     @staticmethod
     def from_table(table, offsets, min_voxels: int = 1, access=None, dims=None, shape=None, reach=None,
                    tool=None, contacts=None, walls=None, thin: bool = True,
-                   recognized=None) -> "list[list[FeatureInstance]]":
+                   recognized=None, split=None) -> "list[list[FeatureInstance]]":
         """Per-sample record lists from an instance table int64 ``[T, 13]`` and its ``offsets``
         ``[N + 1]`` (tensors or arrays).  Components of fewer than ``min_voxels`` voxels are left
         out; the others keep their ``id``.  ``access``: the access table int64 ``[T, 8]`` of the
@@ -251,7 +256,8 @@ class FeatureInstance:
         the wall table int64 ``[T, 5]`` of the same rows, or None; it needs ``shape`` too, and with
         ``thin=False`` (no limit was asked for) ``thin_voxels`` stays None.  ``recognized``: ``(cls,
         prob)`` of ``ops.isolate.recognize_table``, int64 and float32 ``[T]`` of the same rows, or None;
-        a row with ``cls < 0`` was not classified and keeps None."""
+        a row with ``cls < 0`` was not classified and keeps None.  ``split``: ``(parent_component, peak2)``
+        of ``ops.watershed.split_instances``, int64 ``[T]`` of the same rows, or None."""
         tab = np.asarray(table.cpu() if hasattr(table, "cpu") else table, dtype=np.int64).reshape(-1, 13)
         off = np.asarray(offsets.cpu() if hasattr(offsets, "cpu") else offsets, dtype=np.int64)
         acc = None
@@ -302,6 +308,11 @@ class FeatureInstance:
             rec_cls, rec_prob = (np.asarray(t.cpu() if hasattr(t, "cpu") else t).reshape(-1) for t in recognized)
             if len(rec_cls) != len(tab) or len(rec_prob) != len(tab):
                 raise ValueError("from_table: the recognized classes do not belong to this instance table")
+        comp = None
+        if split is not None:
+            comp, peak = (np.asarray(t.cpu() if hasattr(t, "cpu") else t, dtype=np.int64).reshape(-1) for t in split)
+            if len(comp) != len(tab) or len(peak) != len(tab):
+                raise ValueError("from_table: the split columns do not belong to this instance table")
         out = []
         for n in range(len(off) - 1):
             recs = []
@@ -335,6 +346,8 @@ class FeatureInstance:
                         rec.gap_to = other - int(off[n]) + 1
                 if rec_cls is not None and rec_cls[k] >= 0:
                     rec.recognized, rec.recognized_prob = int(rec_cls[k]), float(rec_prob[k])
+                if comp is not None:
+                    rec.component, rec.peak2 = int(comp[k]), int(peak[k])
                 recs.append(rec)
             out.append(recs)
         return out
