@@ -11,7 +11,7 @@ __version__ = "0.1.0"
 _API = ("train", "classify", "segment", "extract_features", "label_components", "evaluate", "evaluate_segmentation",
         "evaluate_features", "match_features", "generate_parts", "voxelize", "distance_transform", "EDT_INF", "load", "save",
         "build_model", "search", "TrainResult", "tool_reach", "nearest_instances", "isolate_features",
-        "recognize", "split_features")
+        "recognize", "split_features", "label_mesh")
 
 
 def __getattr__(name):

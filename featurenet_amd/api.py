@@ -282,7 +282,8 @@ def evaluate_segmentation(model, x, y, batch_size: int = 32, device=None, packed
 def extract_features(model, x, batch_size: int = 32, device=None, packed_size: int | None = None,
                      background: int | None = 0, connectivity: int = 6, min_voxels: int = 1,
                      return_ids: bool = False, access: bool = False, dimensions: bool = False, tool=None,
-                     contacts: bool = False, walls=False, classifier=None):
+                     contacts: bool = False, walls=False, classifier=None, meshes=None, fit="bbox",
+                     margin: float = 0):
     """The machining features of each part -> (one list of :class:`FeatureInstance` per sample,
     ids int32 [N, S, S, S] or None).
 
@@ -340,6 +341,10 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
     (``ops.isolate``, the FeatureNet paper's recipe), ``recognized_prob`` that class's probability, and
     ``agrees`` says whether ``cls == recognized + 1``.  The parts are made and classified on the model's
     device; two numbers per component cross to the host.
+
+    With ``meshes`` -- the meshes ``x`` was voxelized from, as for :func:`voxelize`, with the ``fit`` and
+    ``margin`` used there -- every record also says which triangles of its part's mesh are its own:
+    ``faces`` holds the indices of the triangles that :func:`label_mesh` gives to its ``id``.
     """
     from .utils.seginstances import FeatureInstance, tool_thresholds
 
@@ -366,7 +371,8 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
             xb = unpack_voxels(xb, packed_size)
         xb = xb.to(torch.bfloat16) if dev.type == "cuda" else xb.float()
         table, offsets, idb, *more = model.instances(xb, background=background, connectivity=connectivity,
-                                                     want_ids=return_ids or classifier is not None,
+                                                     want_ids=return_ids or classifier is not None
+                                                     or meshes is not None,
                                                      want_access=access, want_dims=dimensions,
                                                      want_reach=thresholds, want_contacts=contacts,
                                                      want_walls=limit2)
@@ -388,8 +394,12 @@ def extract_features(model, x, batch_size: int = 32, device=None, packed_size: i
                                             shape=tuple(xb.shape[1:4]),
                                             reach=more[-1] if thresholds is not None else None, tool=thresholds,
                                             contacts=pairs, walls=wall, thin=walls is not True, recognized=seen)
-        if return_ids:
+        if return_ids or meshes is not None:
             ids.append(idb.cpu())
+    if meshes is not None:
+        S = model.input_size
+        _assign_faces(feats, torch.cat(ids) if ids else torch.zeros((0, S, S, S), dtype=torch.int32), meshes, fit,
+                      margin, dev, "extract_features()")
     if not return_ids:
         return feats, None
     S = model.input_size
@@ -610,7 +620,7 @@ def isolate_features(ids, features=None, size: int | None = None, occupancy=None
 def recognize(classifier, voxels, stock: str = "grid", connectivity: int = 6, min_voxels: int = 1,
               return_ids: bool = False, return_labels: bool = False, batch_size: int = 256, device=None,
               access: bool = False, dimensions: bool = False, tool=None, contacts: bool = False, walls=False,
-              split=None):
+              split=None, meshes=None, fit="bbox", margin: float = 0):
     """The features of each part by the single-feature classifier alone, the multi-feature recipe of
     the FeatureNet paper -> ``(features, ids or None, labels or None)``: one list of
     :class:`FeatureInstance` per sample, ids int32 ``[N, D, H, W]`` with ``return_ids`` and labels
@@ -631,7 +641,8 @@ def recognize(classifier, voxels, stock: str = "grid", connectivity: int = 6, mi
     of the distance to the material before it is isolated and classified, as :func:`split_features` does
     -- a hole in a pocket floor then becomes a record of its own, with ``component`` and ``peak2`` -- and
     None leaves touching features as one.  ``access``, ``dimensions``, ``tool``, ``contacts`` and
-    ``walls`` as for :func:`extract_features`; with ``split`` they describe the pieces.
+    ``walls`` as for :func:`extract_features`; with ``split`` they describe the pieces.  ``meshes`` (with
+    ``fit`` and ``margin``), the meshes ``voxels`` was made from, fills every record's ``faces`` as there.
     """
     from .ops import ccl, isolate
     from .utils.seginstances import FeatureInstance, tool_thresholds
@@ -666,6 +677,8 @@ def recognize(classifier, voxels, stock: str = "grid", connectivity: int = 6, mi
     more = _geometry_tables(ids, table, offsets, occ, access, dimensions, thresholds, contacts, limit2, d2=d2)
     feats = FeatureInstance.from_table(table, offsets, min_voxels, shape=tuple(occ.shape[1:]), tool=thresholds,
                                        thin=walls is not True, recognized=(cls, prob), split=cut, **more)
+    if meshes is not None:
+        _assign_faces(feats, ids, meshes, fit, margin, device, "recognize()")
     labels = None
     if return_labels:
         lut = torch.cat([table.new_zeros(1), table[:, 1]])                      # 0: no component
@@ -943,6 +956,27 @@ def _mesh_triangles(mesh) -> np.ndarray:
     return tris
 
 
+def _mesh_lattice(meshes, size: int, fit, margin):
+    """The ``meshes`` of :func:`voxelize` on the lattice of a ``size``^3 grid -> ``(single, tris int32
+    [T, 9], offsets int32 [N + 1], origins, voxel sizes)``; ``single``: one mesh was given, not a list."""
+    from .ops import voxelize as vx
+
+    single = isinstance(meshes, (str, Path, np.ndarray, torch.Tensor)) or \
+        (isinstance(meshes, tuple) and len(meshes) == 2 and not isinstance(meshes[0], (str, Path, tuple)))
+    if single and isinstance(meshes, (np.ndarray, torch.Tensor)) and meshes.ndim == 4:
+        single, meshes = False, list(meshes)             # [N, F, 3, 3]: N meshes of F triangles
+    lattice, origins, sizes = [], [], []
+    for mesh in ([meshes] if single else list(meshes)):
+        q, origin, voxel_size = vx.quantize(_mesh_triangles(mesh), size, fit, margin)
+        lattice.append(q.reshape(-1, 9))
+        origins.append(origin)
+        sizes.append(voxel_size)
+    counts = [len(q) for q in lattice]
+    tris = torch.from_numpy(np.concatenate(lattice) if lattice else np.zeros((0, 9), np.int32))
+    offsets = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32)
+    return single, tris, offsets, origins, sizes
+
+
 def voxelize(meshes, size: int = 64, fit="bbox", margin: float = 0, device=None, packed: bool = False,
              return_info: bool = False):
     """Triangle meshes -> occupancy uint8 ``[N, S, S, S]`` (1 = material, indexed ``[n, z, y, x]``),
@@ -967,25 +1001,72 @@ def voxelize(meshes, size: int = 64, fit="bbox", margin: float = 0, device=None,
 
     if device is None:
         device = "cuda" if torch.cuda.is_available() else "cpu"
-    single = isinstance(meshes, (str, Path, np.ndarray, torch.Tensor)) or \
-        (isinstance(meshes, tuple) and len(meshes) == 2 and not isinstance(meshes[0], (str, Path, tuple)))
-    if single and isinstance(meshes, (np.ndarray, torch.Tensor)) and meshes.ndim == 4:
-        single, meshes = False, list(meshes)             # [N, F, 3, 3]: N meshes of F triangles
-    lattice, origins, sizes = [], [], []
-    for mesh in ([meshes] if single else list(meshes)):
-        q, origin, voxel_size = vx.quantize(_mesh_triangles(mesh), size, fit, margin)
-        lattice.append(q.reshape(-1, 9))
-        origins.append(origin)
-        sizes.append(voxel_size)
-    counts = [len(q) for q in lattice]
-    tris = torch.from_numpy(np.concatenate(lattice) if lattice else np.zeros((0, 9), np.int32))
-    offsets = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32)
+    _, tris, offsets, origins, sizes = _mesh_lattice(meshes, size, fit, margin)
     vox, leaks = vx.voxelize(tris, offsets, size, device=device, packed=packed)
     vox = vox.cpu().numpy()
     if not return_info:
         return vox
     return vox, {"leaks": leaks.cpu().numpy(), "origin": np.asarray(origins, np.float64).reshape(-1, 3),
                  "voxel_size": np.asarray(sizes, np.float64)}
+
+
+def label_mesh(meshes, volume, fit="bbox", margin: float = 0, device=None, return_votes: bool = False):
+    """Which value of a voxel volume lies against each triangle of the mesh the volume was made
+    from -> one int32 ``[F_i]`` array of winners per mesh (the array itself for a single mesh): the
+    way from instance ids or labels on the grid back to the faces of the CAD model.
+
+    ``meshes`` as for :func:`voxelize`; ``volume`` is ``[N, S, S, S]`` or, for one mesh, ``[S, S,
+    S]``: the ``ids`` of :func:`extract_features` / :func:`recognize` / :func:`label_components`
+    (any integer dtype that fits int32) or uint8 labels of :func:`segment`, 0 = nothing.  The meshes
+    are placed by the same ``quantize`` call as in :func:`voxelize`, so the same ``fit`` and
+    ``margin`` -- or ``fit=(origin, voxel_size)`` from its ``return_info`` -- land the triangles on
+    the voxels they made.  Each triangle is looked at along the dominant axis of its normal: in
+    every voxel column whose centre it covers, the voxel just before the surface and the one just
+    behind it vote with their value; a triangle too small to cover a column centre votes once at
+    its centroid.  The value with the most votes wins, the lowest on a tie, 0 with none: winding
+    and vertex order do not matter, and material (0 in an id volume) does not vote.  Integer
+    arithmetic on the lattice, the same on every device: ``device`` (default: the GPU when there
+    is one) chooses between the ``mesh_votes`` kernel and the host path.
+
+    ``return_votes`` adds, per mesh, the int32 ``[F_i, 3]`` rows ``winner, votes, covered``
+    (``covered``: the columns the triangle covers; 0: it voted at its centroid)."""
+    from .ops import meshlabel
+
+    vt = torch.as_tensor(np.asarray(volume)) if not isinstance(volume, torch.Tensor) else volume
+    if vt.is_floating_point() or vt.is_complex() or vt.dtype == torch.bool:
+        raise ValueError(f"label_mesh(): volume must be integers, not {vt.dtype}")
+    if vt.dim() == 3:
+        vt = vt.unsqueeze(0)
+    if vt.dim() != 4 or len(set(vt.shape[1:])) != 1:
+        raise ValueError(f"label_mesh(): volume must be [N, S, S, S] or [S, S, S], not {tuple(vt.shape)}")
+    if vt.dtype not in (torch.uint8, torch.int32):
+        if vt.numel() and (int(vt.min()) < -2 ** 31 or int(vt.max()) >= 2 ** 31):
+            raise ValueError("label_mesh(): the values of volume must fit int32")
+        vt = vt.to(torch.int32)
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    single, tris, offsets, _, _ = _mesh_lattice(meshes, int(vt.shape[1]), fit, margin)
+    if offsets.numel() - 1 != vt.shape[0]:
+        raise ValueError(f"label_mesh(): {offsets.numel() - 1} meshes but {vt.shape[0]} volumes")
+    rows = meshlabel.mesh_votes(tris, offsets, vt, device=device).cpu().numpy()
+    rows = [rows[a:b] for a, b in zip(offsets[:-1].tolist(), offsets[1:].tolist())]
+    winners = [np.ascontiguousarray(r[:, 0]) for r in rows]
+    if single:
+        return (winners[0], rows[0]) if return_votes else winners[0]
+    return (winners, rows) if return_votes else winners
+
+
+def _assign_faces(feats, ids, meshes, fit, margin, device, what: str) -> None:
+    """The ``meshes=`` option of :func:`extract_features` and :func:`recognize`: ``FeatureInstance.faces``
+    from :func:`label_mesh` of the meshes against ``ids`` (a tensor, every sample of the call)."""
+    from .utils.seginstances import assign_faces
+
+    winners = label_mesh(meshes, ids, fit=fit, margin=margin, device=device)
+    if isinstance(winners, np.ndarray):
+        winners = [winners]
+    if len(winners) != len(feats):
+        raise ValueError(f"{what}: {len(winners)} meshes but {len(feats)} samples")
+    assign_faces(feats, winners)
 
 
 def evaluate(model, x, y, batch_size: int = 256, packed_size: int | None = None) -> float:

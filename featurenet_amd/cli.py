@@ -420,6 +420,44 @@ def cmd_voxelize(a) -> int:
     return 0
 
 
+def cmd_label_mesh(a) -> int:
+    import numpy as np
+
+    from . import api
+
+    ids = np.load(a.ids, allow_pickle=False)
+    if ids.ndim == 4:
+        if not 0 <= a.index < len(ids):
+            raise SystemExit(f"label-mesh: --index {a.index} outside 0..{len(ids) - 1}")
+        ids = ids[a.index]
+    if ids.ndim != 3:
+        raise SystemExit(f"label-mesh: {a.ids} holds an array of shape {ids.shape}, not [S, S, S] or [N, S, S, S]")
+    fit = "bbox" if a.voxel_size is None else (a.origin, a.voxel_size)
+    if a.fit and a.fit != ["bbox"]:
+        try:
+            *origin, voxel_size = [float(v) for v in a.fit]
+            assert len(origin) == 3
+        except (ValueError, AssertionError):
+            raise SystemExit(f"label-mesh: --fit is 'bbox' or OX OY OZ VOXEL_SIZE, not {' '.join(a.fit)!r}")
+        fit = (origin, voxel_size)
+    winners, rows = api.label_mesh(a.mesh, ids, fit=fit, margin=a.margin, device=a.device or None, return_votes=True)
+    np.save(a.output, winners)
+    values, counts = np.unique(winners, return_counts=True)
+    doc = {"mesh": a.mesh, "triangles": int(len(winners)), "labelled": int((winners != 0).sum()),
+           "centroid_votes": int((rows[:, 2] == 0).sum()),
+           "faces": {str(int(v)): int(c) for v, c in zip(values, counts) if v != 0}}
+    if a.obj:
+        from .utils.voxelmesh import write_labelled_obj
+
+        write_labelled_obj(a.obj, api._mesh_triangles(a.mesh), winners)
+    summary = json.dumps(doc)
+    if a.json:
+        with open(a.json, "w") as f:
+            f.write(summary + "\n")
+    print(summary)
+    return 0
+
+
 def cmd_export_stl(a) -> int:
     import numpy as np
 
@@ -734,6 +772,24 @@ def build_parser() -> argparse.ArgumentParser:
     vx.add_argument("--json", default="", metavar="OUT", help="also write leaks and transforms to this file")
     vx.add_argument("--binvox", default="", metavar="DIR", help="also write one .binvox per mesh into this folder")
     vx.set_defaults(fn=cmd_voxelize)
+
+    lm = sub.add_parser("label-mesh", help="instance ids or labels on the grid (.npy) -> the id against each triangle of the STL")
+    lm.add_argument("mesh", help="the binary or ASCII STL file the volume was voxelized from")
+    lm.add_argument("ids", help="[S, S, S] or [N, S, S, S] integer array (.npy): instance ids or labels, 0 = nothing")
+    lm.add_argument("--index", type=int, default=0, help="which volume of an [N, S, S, S] array")
+    lm.add_argument("--fit", nargs="+", default=[], metavar="FIT",
+                    help="'bbox' (default) or OX OY OZ VOXEL_SIZE, the origin and voxel_size that voxelize --json reports")
+    lm.add_argument("--margin", type=float, default=0, help="as given to voxelize")
+    lm.add_argument("--origin", type=float, nargs=3, default=[0.0, 0.0, 0.0], metavar=("X", "Y", "Z"),
+                    help="with --voxel-size: the model-space corner of voxel (0, 0, 0)")
+    lm.add_argument("--voxel-size", type=float, default=None,
+                    help="edge of a voxel in model units (default: fit the mesh's bounding box to the grid, as voxelize does)")
+    lm.add_argument("--device", default="", help="cuda / cpu (default: the GPU when there is one)")
+    lm.add_argument("-o", "--output", required=True, help="winners, int32 [F] (.npy)")
+    lm.add_argument("--json", default="", metavar="OUT", help="also write the summary to this file")
+    lm.add_argument("--obj", default="", metavar="OUT",
+                    help="also write the triangles as an OBJ with one group per feature (g feature_<id>, g unlabelled)")
+    lm.set_defaults(fn=cmd_label_mesh)
 
     xs = sub.add_parser("export-stl", help="boundary of a voxel volume (.npy) -> STL")
     xs.add_argument("input", help="[S, S, S] or [N, S, S, S] array (.npy)")

@@ -49,6 +49,8 @@ int fn_partgen_chunk();
 int fn_partgen_carve(const void*, void*, void*, void*, void*, int, int, int, hipStream_t);
 int fn_voxelize_planes(int);
 int fn_voxelize_tris(const void*, const void*, void*, void*, void*, int, int, int, int, hipStream_t);
+int fn_mesh_votes_thread_cols();
+int fn_mesh_votes(const void*, const void*, const void*, void*, void*, int, int, int, int, int, hipStream_t);
 void fn_overlap_chunk(int*);
 int fn_overlap_pairs(const void*, const void*, const void*, const void*, void*, void*, void*, int, long long, int,
                      long long, long long, hipStream_t);
@@ -1031,6 +1033,23 @@ PYBIND11_MODULE(_C, m) {
         "voxelize_tris");
   }, py::arg("tris"), py::arg("offsets"), py::arg("occ"), py::arg("packed"), py::arg("leaks_part"), py::arg("N"),
      py::arg("T"), py::arg("S"), py::arg("zs"), py::arg("st"), py::arg("ext"));
+  // mesh labels (meshlabel.hip): tris / offsets as voxelize_tris, vol int32 (elem = 4) or uint8 (elem = 1)
+  // [N][S][S][S] -> votes int32 [T][3] = winner, votes, covered; thr: a triangle whose box holds more than thr
+  // columns takes the wave form (-1: every triangle; at most mesh_votes_thread_cols()); wide: int32 scratch [T + 1];
+  // ext = {numel(tris), numel(offsets), numel(vol), numel(votes), numel(wide)}
+  m.def("mesh_votes_thread_cols", []() { return fn_mesh_votes_thread_cols(); });
+  m.def("mesh_votes", [](uintptr_t tris, uintptr_t offsets, uintptr_t vol, uintptr_t votes, uintptr_t wide, int N, int T,
+                         int size, int elem, int thr, uintptr_t st, std::vector<long long> ext) {
+    fits(ext, 0, prod({T, 9}), "mesh_votes", "tris");
+    fits(ext, 1, N < 0 ? -1 : N + 1LL, "mesh_votes", "offsets");
+    fits(ext, 2, prod({N, size, size, size}), "mesh_votes", "vol");
+    fits(ext, 3, prod({T, 3}), "mesh_votes", "votes");
+    fits(ext, 4, T < 0 ? -1 : T + 1LL, "mesh_votes", "wide");
+    chk(fn_mesh_votes(P<const void*>(tris), P<const void*>(offsets), P<const void*>(vol), P<void*>(votes),
+                      P<void*>(wide), N, T, size, elem, thr, S(st)),
+        "mesh_votes");
+  }, py::arg("tris"), py::arg("offsets"), py::arg("vol"), py::arg("votes"), py::arg("wide"), py::arg("N"),
+     py::arg("T"), py::arg("S"), py::arg("elem"), py::arg("thr"), py::arg("st"), py::arg("ext"));
   // part: fp32 scratch of pw_wgrad_blocks(M, K, N) x N x K floats (per-workgroup partials)
   m.def("pw_wgrad", [](uintptr_t dy, uintptr_t x, uintptr_t dw, long long M, int K, int N, uintptr_t st,
                        uintptr_t psc, uintptr_t psh, int pact, uintptr_t part, long long part_n) {

@@ -3,6 +3,8 @@
 //
 //   voxelize_tris(tris int32 [T, 9], offsets int32 [N + 1], size, threads)
 //       -> (occupancy uint8 [N, S, S, S], leaks int64 [N])
+//   mesh_votes(tris, offsets, vol int32 | uint8 [N, S, S, S], threads) -> int32 [T, 3]: the host path of
+//       kernels/meshlabel.hip, winner, votes, covered per triangle (the rule: ../shared/voxelize.h)
 //   read_stl(path) -> float32 [F, 3, 3]; write_stl(path, tris, binary = true)
 //
 // A binary STL is 80 header bytes, a uint32 triangle count n and n records of 50 bytes (normal,
@@ -91,6 +93,105 @@ py::tuple voxelize_tris(py::array_t<int32_t, py::array::c_style | py::array::for
     for (int s = 0; s < kSlabs; ++s) pl[n] += part[(size_t)n * kSlabs + s];
   }
   return py::make_tuple(occ, leaks);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Mesh labels
+// ---------------------------------------------------------------------------------------------
+void check_mesh(const char* what, const py::array& tris, const py::array& offsets, const int32_t* tr,
+                const int32_t* off) {
+  const std::string w(what);
+  if (tris.ndim() != 2 || tris.shape(1) != 9) throw std::runtime_error(w + ": tris must be int32 [T, 9]");
+  if (offsets.ndim() != 1 || offsets.shape(0) < 1) throw std::runtime_error(w + ": offsets must be int32 [N + 1]");
+  const int N = (int)offsets.shape(0) - 1;
+  const long long T = tris.shape(0);
+  if (off[0] != 0 || off[N] != T) throw std::runtime_error(w + ": offsets must run from 0 to T");
+  for (int n = 0; n < N; ++n)
+    if (off[n + 1] < off[n]) throw std::runtime_error(w + ": offsets must not decrease");
+  for (long long i = 0; i < T * 9; ++i)
+    if (tr[i] > VX_MAX_COORD || tr[i] < -VX_MAX_COORD)
+      throw std::runtime_error(w + ": a coordinate exceeds 8192 lattice units");
+}
+
+template <typename V>
+void mesh_votes_rows(const int32_t* tr, const int32_t* off, const V* vol, int32_t* out, int N, int S, int threads) {
+  constexpr int kChunk = 256;                    // triangles per work item
+  std::vector<std::pair<int, int>> items;        // (mesh, first triangle)
+  for (int n = 0; n < N; ++n)
+    for (int i = off[n]; i < off[n + 1]; i += kChunk) items.emplace_back(n, i);
+  parallel_for((int)items.size(), threads, [&](int item) {
+    const int n = items[item].first, first = items[item].second;
+    const int last = std::min(first + kChunk, (int)off[n + 1]);
+    const V* v = vol + (size_t)n * S * S * S;
+    const int stride[3] = {1, S, S * S};
+    std::vector<int> seen;
+    for (int i = first; i < last; ++i) {
+      int32_t* row = out + (size_t)i * 3;
+      row[0] = row[1] = row[2] = 0;
+      int q[9];
+      const int m = vx_dominant(tr + (size_t)i * 9, q);
+      if (m < 0) continue;
+      const int sm = stride[m], su = stride[(m + 1) % 3], sv = stride[(m + 2) % 3];
+      seen.clear();
+      auto look = [&](int k, int iu, int iv) {
+        if (iu < 0 || iu >= S || iv < 0 || iv >= S) return;
+        for (int kk = k - 1; kk <= k; ++kk)
+          if (kk >= 0 && kk < S) {
+            const int val = (int)v[(size_t)kk * sm + (size_t)iu * su + (size_t)iv * sv];
+            if (val != 0) seen.push_back(val);
+          }
+      };
+      VxTri t;
+      int covered = 0;
+      if (vx_setup(q, S, 0, S - 1, t))
+        for (int iv = t.z0; iv <= t.z1; ++iv)
+          for (int iu = t.y0; iu <= t.y1; ++iu)
+            if (vx_covers(t, iu, iv)) {
+              ++covered;
+              look(vx_kcross(t, S, iu, iv), iu, iv);
+            }
+      if (covered == 0) {
+        int k, iu, iv;
+        vx_centroid(q, k, iu, iv);
+        look(k, iu, iv);
+      }
+      std::sort(seen.begin(), seen.end());
+      int best = 0, votes = 0;
+      for (size_t a = 0; a < seen.size();) {
+        size_t b = a;
+        while (b < seen.size() && seen[b] == seen[a]) ++b;
+        if (vx_beats(seen[a], (int)(b - a), best, votes)) best = seen[a], votes = (int)(b - a);
+        a = b;
+      }
+      row[0] = best, row[1] = votes, row[2] = covered;
+    }
+  });
+}
+
+py::array_t<int32_t> mesh_votes(py::array_t<int32_t, py::array::c_style | py::array::forcecast> tris,
+                                py::array_t<int32_t, py::array::c_style | py::array::forcecast> offsets, py::array vol,
+                                int threads) {
+  check_mesh("mesh_votes", tris, offsets, tris.data(), offsets.data());
+  const int N = (int)offsets.shape(0) - 1;
+  const bool i32 = vol.dtype().is(py::dtype::of<int32_t>()), u8 = vol.dtype().is(py::dtype::of<uint8_t>());
+  if (!i32 && !u8) throw std::runtime_error("mesh_votes: vol must be int32 or uint8");
+  if (vol.ndim() != 4 || vol.shape(0) != N || vol.shape(1) != vol.shape(2) || vol.shape(2) != vol.shape(3))
+    throw std::runtime_error("mesh_votes: vol must be [N, S, S, S] with one volume per mesh");
+  if (!(vol.flags() & py::array::c_style)) throw std::runtime_error("mesh_votes: vol must be contiguous");
+  const long long size = vol.shape(1);
+  if (size < 8 || size > VX_MAX_S || size % 8 != 0)
+    throw std::runtime_error("mesh_votes: size must be a multiple of 8 in [8, 256]");
+  py::array_t<int32_t> out(std::vector<py::ssize_t>{tris.shape(0), 3});
+  int32_t* po = out.mutable_data();
+  const int32_t* tr = tris.data();
+  const int32_t* off = offsets.data();
+  const void* pv = vol.data();
+  {
+    py::gil_scoped_release nogil;
+    if (i32) mesh_votes_rows(tr, off, static_cast<const int32_t*>(pv), po, N, (int)size, threads);
+    else mesh_votes_rows(tr, off, static_cast<const uint8_t*>(pv), po, N, (int)size, threads);
+  }
+  return out;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -215,6 +316,9 @@ void register_mesh(py::module_& m) {
   m.def("voxelize_tris", &voxelize_tris, py::arg("tris"), py::arg("offsets"), py::arg("size"), py::arg("threads") = 0,
         "meshes on the 16-units-per-voxel lattice, int32 [T, 9] + offsets int32 [N + 1] -> (occupancy uint8 "
         "[N, S, S, S], leaks int64 [N])");
+  m.def("mesh_votes", &mesh_votes, py::arg("tris"), py::arg("offsets"), py::arg("vol"), py::arg("threads") = 0,
+        "meshes as for voxelize_tris and vol int32 | uint8 [N, S, S, S] -> int32 [T, 3]: the value that lies against "
+        "each triangle, its votes and the columns the triangle covers");
   m.def("read_stl", &read_stl, py::arg("path"), "binary or ASCII STL -> float32 [F, 3, 3]");
   m.def("write_stl", &write_stl, py::arg("path"), py::arg("tris"), py::arg("binary") = true);
 }

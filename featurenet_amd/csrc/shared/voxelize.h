@@ -104,3 +104,56 @@ VX_HD int vx_kmin(const VxTri& s, int S, int iy, int iz) {
   if ((k - 1) * den >= num) --k;
   return k < 0 ? 0 : k > S ? S : (int)k;
 }
+
+// The same quotient clamped to [-1, S + 1] only: ceil((x_hit - 8) / 16), the first voxel whose
+// centre is not before the crossing, for a caller that looks at voxels k - 1 and k on both sides
+// of the surface (-1 and S + 1: both of them lie outside the grid, on that side).
+VX_HD int vx_kcross(const VxTri& s, int S, int iy, int iz) {
+  const long long nx = s.nx;
+  const long long A = (long long)s.ny * (VX_U * iy + VX_HALF - s.ay) + (long long)s.nz * (VX_U * iz + VX_HALF - s.az);
+  const long long num = (long long)s.ax * nx - A - VX_HALF * nx, den = VX_U * nx;
+  if (num <= -den) return -1;
+  if (num > den * S) return S + 1;
+  long long k = (long long)((double)num / (double)den);       // the quotient truncated, or one off
+  if (k * den < num) ++k;
+  if ((k - 1) * den >= num) --k;
+  return (int)k;                                               // -den < num <= den S: 0..S
+}
+
+// ---------------------------------------------------------------------------------------------
+// Mesh labels: which value of a volume lies against a triangle (kernels/meshlabel.hip and
+// mesh_votes of runtime/mesh.cpp; the torch oracle is reference.mesh_votes).  The triangle is
+// turned so that the dominant axis m of its normal (the first of x, y, z with the largest
+// |component|) becomes the x of the rays above, u = (m + 1) % 3 its y and v = (m + 2) % 3 its z:
+// the projection has area, and columns run along m.
+// ---------------------------------------------------------------------------------------------
+
+// q = the triangle with every vertex as (p[m], p[u], p[v]) -> m, or -1 when the normal is zero.
+VX_HD int vx_dominant(const int* t, int* q) {
+  const int e1[3] = {t[3] - t[0], t[4] - t[1], t[5] - t[2]}, e2[3] = {t[6] - t[0], t[7] - t[1], t[8] - t[2]};
+  int n[3];                                      // |edge| <= 2^14, a product <= 2^28, a component <= 2^29
+  for (int i = 0; i < 3; ++i) {
+    const int j = i == 2 ? 0 : i + 1, k = j == 2 ? 0 : j + 1;
+    n[i] = e1[j] * e2[k] - e1[k] * e2[j];
+    n[i] = n[i] < 0 ? -n[i] : n[i];
+  }
+  if ((n[0] | n[1] | n[2]) == 0) return -1;
+  const int m = n[0] >= n[1] && n[0] >= n[2] ? 0 : n[1] >= n[2] ? 1 : 2;
+  const int u = m == 2 ? 0 : m + 1, v = u == 2 ? 0 : u + 1;
+  for (int p = 0; p < 3; ++p) q[3 * p] = t[3 * p + m], q[3 * p + 1] = t[3 * p + u], q[3 * p + 2] = t[3 * p + v];
+  return m;
+}
+
+// The one vote of a triangle that covers no column centre, at its centroid: column (iu, iv) =
+// floor(sum / 48) (it may lie outside the grid) and k = ceil((sum_m - 24) / 48).
+VX_HD void vx_centroid(const int* q, int& k, int& iu, int& iv) {
+  const int sm = q[0] + q[3] + q[6], su = q[1] + q[4] + q[7], sv = q[2] + q[5] + q[8];
+  const int off = 48 * 1024;                     // |sum| <= 3 * 8192 < off: the divisions see positives
+  iu = (su + off) / 48 - 1024, iv = (sv + off) / 48 - 1024;
+  k = (sm - 24 + 47 + off) / 48 - 1024;
+}
+
+// the winner of two tallies (value, votes): more votes, then the lower value; votes 0 = none
+VX_HD bool vx_beats(int value, int votes, int best_value, int best_votes) {
+  return votes > best_votes || (votes == best_votes && votes > 0 && value < best_value);
+}

@@ -784,7 +784,95 @@ def voxelize_tris(tris: torch.Tensor, offsets: torch.Tensor, size: int):
     return occ, leaks
 
 
-ISOLATE_NCOL = 14          # n id | box z0 y0 x0 z1 y1 x1 | window z0 y0 x0 Lz Ly Lx
+def mesh_votes(tris: torch.Tensor, offsets: torch.Tensor, vol: torch.Tensor, size: int) -> torch.Tensor:
+    """Which value of ``vol`` lies against each triangle -> int32 ``[T, 3]`` = ``winner, votes,
+    covered``, on the device of ``tris``.
+
+    ``tris`` / ``offsets`` as in :func:`voxelize_tris`; ``vol`` ``[N, S, S, S]`` (indexed ``[n, z,
+    y, x]``; int32 instance ids or uint8 labels, 0 = nothing).  Per triangle ``nrm = (b - a) x (c -
+    a)``; zero: the row is ``(0, 0, 0)``.  ``m`` is the first of x, y, z with the largest ``|nrm|``,
+    ``u = (m + 1) % 3``, ``v = (m + 2) % 3``, and every vertex becomes ``(p[m], p[u], p[v])``: the
+    ``(x, y, z)`` of :func:`voxelize_tris`, whose cover test (tie rule included) says which columns
+    ``(iu, iv)`` in ``[0, S)^2`` the triangle covers.  In a covered column ``k = ceil((x_hit - 8) /
+    16)``, not clamped, and the voxels ``k - 1`` and ``k`` along ``m`` -- one on each side of the
+    surface -- give their value one vote each if they lie in the grid and hold one.  ``covered``
+    counts the covered columns; a triangle with none votes once at its centroid, column ``(floor(
+    sum_u / 48), floor(sum_v / 48))`` (nothing if outside the grid), ``k = ceil((sum_m - 24) / 48)``.
+    ``winner`` is the value with the most votes, the lowest on a tie.  Exact integers (int64
+    throughout): the oracle of ``mesh_votes`` (kernel) and ``_rt.mesh_votes``."""
+    if tris.dim() != 2 or tris.shape[1] != 9 or tris.dtype != torch.int32:
+        raise ValueError(f"mesh_votes: tris must be int32 [T, 9], not {tris.dtype} {tuple(tris.shape)}")
+    if offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("mesh_votes: offsets must be [N + 1]")
+    S, dev = int(size), tris.device
+    off = [int(x) for x in offsets.tolist()]
+    N, T = len(off) - 1, tris.shape[0]
+    if vol.dtype not in (torch.int32, torch.uint8) or tuple(vol.shape) != (N, S, S, S):
+        raise ValueError(f"mesh_votes: vol must be int32 or uint8 [{N}, {S}, {S}, {S}], not {vol.dtype} "
+                         f"{tuple(vol.shape)}")
+    out = torch.zeros(T, 3, dtype=torch.int64, device=dev)
+    centre = 16 * torch.arange(S, device=dev, dtype=torch.int64) + 8
+    pv, pu = (c.reshape(1, -1) for c in torch.meshgrid(centre, centre, indexing="ij"))      # [1, S*S], column = iv*S + iu
+    stride = torch.tensor([1, S, S * S], dtype=torch.int64, device=dev)
+    chunk = max(1, (1 << 21) // (S * S))
+    for n in range(N):
+        flat = vol[n].reshape(-1).to(torch.int64)
+        for lo in range(off[n], off[n + 1], chunk):
+            hi = min(lo + chunk, off[n + 1])
+            t = tris[lo:hi].to(torch.int64).view(-1, 3, 3)
+            nrm = torch.linalg.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0]).abs()
+            m = torch.where((nrm[:, 0] >= nrm[:, 1]) & (nrm[:, 0] >= nrm[:, 2]), 0,
+                            torch.where(nrm[:, 1] >= nrm[:, 2], 1, 2))
+            axes = torch.stack([m, (m + 1) % 3, (m + 2) % 3], 1)                            # [n, 3]: m, u, v
+            q = torch.gather(t, 2, axes.unsqueeze(1).expand(-1, 3, -1))
+            st = stride[axes]                                                               # strides of m, u, v
+            a, b, c = q[:, 0], q[:, 1], q[:, 2]
+            area2 = (b[:, 1] - a[:, 1]) * (c[:, 2] - a[:, 2]) - (b[:, 2] - a[:, 2]) * (c[:, 1] - a[:, 1])
+            flip = (area2 < 0).unsqueeze(1)
+            b, c = torch.where(flip, c, b), torch.where(flip, b, c)
+            live = nrm.any(1)                                                               # then area2 != 0
+            inside = live.unsqueeze(1).expand(-1, S * S).clone()
+            for p, r in ((a, b), (b, c), (c, a)):
+                du, dv = (r[:, 1] - p[:, 1]).unsqueeze(1), (r[:, 2] - p[:, 2]).unsqueeze(1)
+                E = du * (pv - p[:, 2:3]) - dv * (pu - p[:, 1:2])
+                inside &= (E > 0) | ((E == 0) & ((du > 0) | ((du == 0) & (dv < 0))))
+            pl = torch.linalg.cross(b - a, c - a)                                           # pl[:, 0] = |area2|
+            ti, col = inside.nonzero(as_tuple=True)
+            nx = pl[ti, 0]
+            A = pl[ti, 1] * (pu[0, col] - a[ti, 1]) + pl[ti, 2] * (pv[0, col] - a[ti, 2])
+            k = -torch.div(-(a[ti, 0] * nx - A - 8 * nx), 16 * nx, rounding_mode="floor")   # ceil, not clamped
+            covered = torch.bincount(ti, minlength=len(t))
+            # the centroid vote of the triangles that cover nothing
+            lone = (live & (covered == 0)).nonzero().squeeze(1)
+            s = q[lone].sum(1)
+            ti = torch.cat([ti, lone])
+            k = torch.cat([k, -torch.div(-(s[:, 0] - 24), 48, rounding_mode="floor")])
+            iu = torch.cat([col % S, torch.div(s[:, 1], 48, rounding_mode="floor")])
+            iv = torch.cat([col // S, torch.div(s[:, 2], 48, rounding_mode="floor")])
+            column_in = (iu >= 0) & (iu < S) & (iv >= 0) & (iv < S)
+            who, what = [], []
+            for kk in (k - 1, k):
+                ok = column_in & (kk >= 0) & (kk < S)
+                lin = kk[ok] * st[ti[ok], 0] + iu[ok] * st[ti[ok], 1] + iv[ok] * st[ti[ok], 2]
+                val = flat[lin]
+                who.append(ti[ok][val != 0])
+                what.append(val[val != 0])
+            who, what = torch.cat(who), torch.cat(what)
+            rows = out[lo:hi]
+            rows[:, 2] = covered
+            if len(who):
+                pairs, count = torch.unique(torch.stack([who, what], 1), dim=0, return_counts=True)   # by (who, what)
+                order = torch.argsort(count, descending=True, stable=True)                  # most votes first,
+                order = order[torch.argsort(pairs[order, 0], stable=True)]                  # ... within a triangle
+                w = pairs[order, 0]
+                head = torch.ones_like(w, dtype=torch.bool)
+                head[1:] = w[1:] != w[:-1]
+                rows[w[head], 0] = pairs[order, 1][head]
+                rows[w[head], 1] = count[order][head]
+    return out.to(torch.int32)
+
+
+ISOLATE_NCOL = 14         # n id | box z0 y0 x0 z1 y1 x1 | window z0 y0 x0 Lz Ly Lx
 ISOLATE_MAX_S = 256        # longest grid axis and largest output size isolate_instances takes
 _ISOLATE_CHUNK = 1 << 24   # output voxels that isolate_instances gathers at a time
 

@@ -12,7 +12,7 @@ table (``ops.nearest.wall_table``) also how close it comes to another instance w
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from fractions import Fraction
 
 import numpy as np
@@ -95,6 +95,7 @@ class FeatureInstance:
     recognized_prob: float | None = None     # its softmax probability
     component: int | None = None   # the id of the connected component a watershed split cut it from (None: no split)
     peak2: int | None = None       # the largest squared distance to the material inside it, as the split saw it
+    faces: "np.ndarray | None" = field(default=None, compare=False)    # the triangles of the part's mesh that lie against it, ascending (None: no mesh given)
 
     @property
     def agrees(self) -> bool | None:
@@ -212,7 +213,7 @@ class FeatureInstance:
         ``neighbors`` (a list of ``{"id", "face", "faces"}``); with walls also ``gap2``, ``gap_at``,
         ``gap_to``, ``min_wall`` (each None alone in the part) and ``thin_voxels``; with a classifier's
         opinion also ``recognized``, ``recognized_prob`` and ``agrees``; after a watershed split also
-        ``component`` and ``peak2``."""
+        ``component`` and ``peak2``; with a mesh also ``faces``."""
         d = {"id": self.id, "class": self.cls, "voxels": self.voxels, "bbox": list(self.bbox),
              "centroid": list(self.centroid)}
         if self.access is not None:
@@ -238,6 +239,8 @@ class FeatureInstance:
             d.update(recognized=self.recognized, recognized_prob=self.recognized_prob, agrees=self.agrees)
         if self.component is not None:
             d.update(component=self.component, peak2=self.peak2)
+        if self.faces is not None:
+            d.update(faces=[int(i) for i in self.faces])
         return d
 
     @staticmethod
@@ -351,3 +354,16 @@ class FeatureInstance:
                 recs.append(rec)
             out.append(recs)
         return out
+
+
+def assign_faces(features, winners) -> None:
+    """Fill ``FeatureInstance.faces`` of every record: ``features`` is one list of records per
+    sample and ``winners`` one int32 ``[F_i]`` array per sample (``label_mesh``'s: the id that lies
+    against each triangle of the sample's mesh, 0 for none).  A record gets the indices of the
+    triangles its id won, ascending; ids without a record keep their triangles to themselves."""
+    for recs, win in zip(features, winners):
+        win = np.asarray(win)
+        order = np.argsort(win, kind="stable")
+        start = np.concatenate([[0], np.cumsum(np.bincount(win, minlength=1))])
+        for rec in recs:
+            rec.faces = order[start[rec.id]:start[rec.id + 1]] if rec.id + 1 < len(start) else order[:0]

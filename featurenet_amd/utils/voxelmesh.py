@@ -34,6 +34,26 @@ def voxels_to_mesh(occ) -> np.ndarray:
     return np.concatenate(out).astype(np.float32) if out else np.zeros((0, 3, 3), np.float32)
 
 
+def write_labelled_obj(path, tris, winners) -> None:
+    """Triangles float ``[F, 3, 3]`` (model units) and their winners ``[F]`` (``fn.label_mesh``) ->
+    a Wavefront OBJ: three ``v`` lines per triangle in the order given, then one group
+    ``g feature_<id>`` per winner, ascending, and last ``g unlabelled`` for winner 0 (there even if
+    empty); a group's ``f`` lines name the triangles it holds (triangle ``i`` is ``f 3i+1 3i+2 3i+3``)."""
+    tris, winners = np.asarray(tris, np.float64), np.asarray(winners)
+    if tris.ndim != 3 or tris.shape[1:] != (3, 3) or winners.shape != (len(tris),):
+        raise ValueError(f"write_labelled_obj: tris must be [F, 3, 3] and winners [F], not {tris.shape} and "
+                         f"{winners.shape}")
+    with open(path, "w") as f:
+        f.write("# featurenet_amd label-mesh\n")
+        for x, y, z in tris.reshape(-1, 3):
+            f.write(f"v {x:.9g} {y:.9g} {z:.9g}\n")
+        values = np.unique(winners)
+        for value in [*values[values != 0], 0]:             # (unlabelled comes last, and always)
+            f.write("g unlabelled\n" if value == 0 else f"g feature_{int(value)}\n")
+            for i in np.nonzero(winners == value)[0]:
+                f.write(f"f {3 * i + 1} {3 * i + 2} {3 * i + 3}\n")
+
+
 def icosphere(subdivisions: int = 2):
     """A unit sphere as ``(vertices float64 [V, 3], faces int64 [F, 3])``: an icosahedron whose
     triangles are split in four ``subdivisions`` times (``F = 20 * 4 ** subdivisions``), the new
